@@ -2,7 +2,7 @@
 """Headline benchmark: cells*permutations / second of an end-to-end ``cna.tl.association``
 (BASELINE.json metric) on synthetic data, HIP path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C3|C2|C5] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C3|C2|C5] [--scaling strong|weak] [--dump-outputs DIR]
 
 A *step* is one full association() call -- NAM diffusion (3 steps) -> QC/selection ->
 residualisation -> Gram/SVD -> global permutation test -> fused local null + FDRs ->
@@ -202,9 +202,10 @@ class stdout_to_stderr:
         os.close(self.saved)
 
 
-def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dataset=None):
+def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dataset=None, keep_outputs=False):
     """Generate the dataset of `name`, run the cold call, warm up, time `steps` calls.  Returns a dict of
-    raw measurements (rank 0 fills the JSON from it)."""
+    raw measurements (rank 0 fills the JSON from it); with `keep_outputs`, `outputs` holds what the caller of the
+    timed path has after its last timed step (see dump_outputs)."""
     import warnings
     import cna_amd as cna
     from cna_amd import synth
@@ -295,6 +296,12 @@ def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dat
         p_last = cna.tl.association(data, y, 'id', **kw)
     sync()
     dt = time.perf_counter() - t0
+    outputs = None
+    if keep_outputs:
+        # copied now: the next call writes data.obs's FDR column in place (and its coef column again)
+        outputs = dict(p=np.array([p_last], dtype=np.float64),
+                       coef=np.array(data.obs['coef'].values, dtype=np.float64),
+                       coef_fdr=np.array(data.obs['coef_fdr'].values, dtype=np.float64))
     eng.prof_enable(False)
     prof_timed = eng.prof()
     eng.prof_reset()
@@ -356,7 +363,27 @@ def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dat
                 per_rank={k_: [round(float(v), 3) for v in per_rank[:, i]] for i, k_ in enumerate(rank_keys)}, pinned=pinned,
                 two_call_path=_two_call_stats(),
                 halo_comm=getattr(eng, 'halo_comm', False), dev_bytes=int(eng.device_bytes()),
-                state_f32=bool(WORKLOAD_OPTS.get(name, {}).get('state_f32')))
+                state_f32=bool(WORKLOAD_OPTS.get(name, {}).get('state_f32')), outputs=outputs)
+
+
+DUMP_LIMIT_BYTES = 60 << 20      # all .npy files of --dump-outputs together, headers included: under 64 MB
+
+
+def dump_outputs(directory, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `outputs` as <directory>/<name>.npy in float64, so that two builds can be compared
+    output for output.  An array larger than an equal share of `limit` is replaced by a sample of its entries: the same
+    positions on every run, and in every array of the same length (numpy's legacy generator, seed 0, in ascending
+    order).  Returns {name: [entries written, entries in the array]}."""
+    os.makedirs(directory, exist_ok=True)
+    keep = (limit // max(len(outputs), 1) - 4096) // 8       # float64 entries per file (4 KB for its .npy header)
+    written = {}
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > keep:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, name + '.npy'), a)
+        written[name] = [int(a.size), int(np.size(outputs[name]))]
+    return written
 
 
 def _two_call_stats():
@@ -708,6 +735,10 @@ def main():
                          'and C3 as well (the "HBM roofline run": ~100 s of host time, ~30 GB) when the host allows it (>= 16 usable cores, >= 64 GB free)')
     ap.add_argument('--details', default=DETAILS_FILE, help='where the full per-kernel tables go (JSON)')
     ap.add_argument('--profile-host', default=None, help='write a cProfile of 3 extra steps to this file')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64, < 64 MB in all): p (the return value), coef and coef_fdr (the data.obs columns it "
+                         "wrote; rank 0's cells); the inputs are the same on every run with the same arguments")
     ap.add_argument('--comm', default='rccl', choices=['rccl', 'shm'],
                     help="shm: plumbing check of the N>1 path on ONE GPU (all ranks on device 0, gloo for the "
                          "rendezvous, the library's shared-memory test communicator instead of RCCL); not a benchmark")
@@ -769,7 +800,10 @@ def main():
 
     steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.workload][0]
     warmup = args.warmup if args.warmup is not None else DEFAULT_STEPS[args.workload][1]
-    m = time_workload(args.workload, args, rank, world, steps, warmup)
+    m = time_workload(args.workload, args, rank, world, steps, warmup, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(args.dump_outputs, m.pop('outputs'))
+        print('bench.py: wrote %s to %s' % (json.dumps(written), args.dump_outputs), file=sys.stderr)
     eng = get_engine()
     weak = None
     if world > 1 and args.scaling == 'strong' and args.workload == 'C4' and not args.no_extra:
