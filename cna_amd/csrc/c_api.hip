@@ -117,6 +117,15 @@ static const char* kKernelNames[CNA_K_COUNT] = {
     if ((c)->auto_pending) CNA_TRY(cna_nam_auto_finish((c), nullptr, nullptr)); \
   } while (0)
 
+// The contract of a pending local-null pass (launched, not yet fetched): should its integer kernel give up, the fetch
+// reruns it in f64 on the X and Zc the launch saw (null_local_collect).  So every entry point that rewrites X or carves
+// c->scratch refuses with CNA_ESTATE until the pass is fetched (or discarded); nothing is queued and no state changes.
+// Entry points on other buffers (Gram, F-tests, the coefficient column, the FDR copy) may run in between.
+#define NO_NULL_PENDING(c, who)                                                                      \
+  do {                                                                                               \
+    if ((c)->null_pending) CNA_FAIL(CNA_ESTATE, who ": a local-null pass is still pending: fetch it first"); \
+  } while (0)
+
 // scratch layout helper: carve 256-byte aligned pieces out of c->scratch
 struct Carver {
   char* base;
@@ -138,6 +147,7 @@ static int64_t carve_bytes(std::initializer_list<int64_t> sizes) {
 
 // concatenate count_local doubles from every rank (rank order) into a host buffer
 static int ragged_gather(cna_ctx* c, const double* src_dev, int64_t count_local, double* out, int64_t n_expected) {
+  NO_NULL_PENDING(c, "cna_fetch_cell_stat / cna_allgather_host");
   CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, 256 * 2 + 8 * c->nranks));
   int64_t* cnt_dev = (int64_t*)c->scratch;
   std::vector<int64_t> cnt(c->nranks, 0);
@@ -1166,6 +1176,7 @@ static int stat_median_device(cna_ctx* c, bool qc, double* out3) {
 
 int cna_stat_median(cna_ctx* c, double* median_out) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_stat_median");
   AUTO_FINISH(c);
   if (!median_out) CNA_FAIL(CNA_EINVAL, "cna_stat_median: null output");
   if (getenv("CNA_MEDIAN_HOST")) {            // the first implementation: digit choice on the host, 16 round trips
@@ -1210,6 +1221,7 @@ int cna_stat_qc(cna_ctx* c, double* median_out, double* threshold_out, int64_t* 
 // --------------------------------------------------------------------- dense diffusion
 int cna_dense_load(cna_ctx* c, const double* s_local, int m) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_dense_load");
   AUTO_FINISH(c);
   if (!c->have_colsum) CNA_FAIL(CNA_ESTATE, "cna_dense_load needs cna_colsums");
   if (m < 1 || m > 1024) CNA_FAIL(CNA_EINVAL, "dense state must have 1..1024 columns");
@@ -1255,6 +1267,7 @@ int cna_dense_fetch(cna_ctx* c, double* out) {
 // ------------------------------------------------------------------------ QC / select
 int cna_batch_kurtosis(cna_ctx* c, int which, const int32_t* batch_codes, int n_batches) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_batch_kurtosis");
   AUTO_FINISH(c);
   const double* mat;
   int64_t rows;
@@ -1294,6 +1307,7 @@ int cna_batch_kurtosis(cna_ctx* c, int which, const int32_t* batch_codes, int n_
 
 int cna_zero_variance(cna_ctx* c, const int32_t* colmap, int n_sel, uint8_t* flags_out, int64_t* n_zero_out) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_zero_variance");
   AUTO_FINISH(c);
   CNA_TRY(need_nam(c));
   if (!colmap) n_sel = c->N;
@@ -1341,6 +1355,7 @@ static int x_ld(int Nx) {
 
 int cna_select(cna_ctx* c, const int64_t* keep_idx, int64_t n_keep, const int32_t* colmap, int n_sel) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_select");
   AUTO_FINISH(c);
   CNA_TRY(need_nam(c));
   const int64_t nx = keep_idx ? n_keep : c->n_local;
@@ -1405,6 +1420,7 @@ int cna_set_resid_factors(cna_ctx* c, const double* C, const double* W, int r, i
 int cna_select_checked(cna_ctx* c, const int64_t* keep_idx, int64_t n_keep, const int32_t* colmap, int n_sel,
                        int64_t* n_zero_out) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_select_checked");
   AUTO_FINISH(c);
   CNA_TRY(need_nam(c));
   const int64_t nx = keep_idx ? n_keep : c->n_local;
@@ -1461,6 +1477,7 @@ int cna_select_standardized(cna_ctx* c, const int64_t* keep_idx, int64_t n_keep,
 static int select_standardized_impl(cna_ctx* c, const int64_t* keep_idx, int64_t n_keep, const int32_t* colmap, int n_sel,
                                     int64_t* n_zero_out, const double* y, double* max_abs_out, bool* gram_too) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_select_standardized");
   AUTO_FINISH(c);
   if (gram_too) *gram_too = false;
   if (!c->nam_valid && !c->nam_lazy) CNA_FAIL(CNA_ESTATE, "NAM not available");
@@ -1596,6 +1613,12 @@ static int select_standardized_impl(cna_ctx* c, const int64_t* keep_idx, int64_t
       *gram_too = true;
     }
   }
+  if (h != 0 && gram_too && *gram_too) {
+    // rows of zero variance: X is void and so is the Gram matrix queued with it (early, fused or taken under the walk)
+    // -- cna_gram_fetch refuses until the caller's next selection has a Gram matrix of its own
+    c->gram_n = 0;
+    *gram_too = false;
+  }
   return 0;
 }
 
@@ -1678,6 +1701,7 @@ int cna_select_standardized_fused(cna_ctx* c, const int64_t* keep_idx, int64_t n
 
 int cna_upload_x(cna_ctx* c, const double* x_local, int64_t n_rows, int n_cols) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_upload_x");
   if (n_rows < 0 || n_cols < 1 || n_cols > 1024) CNA_FAIL(CNA_EINVAL, "cna_upload_x: bad shape");
   c->nx = n_rows;
   c->Nx = n_cols;
@@ -1703,6 +1727,7 @@ int cna_upload_x(cna_ctx* c, const double* x_local, int64_t n_rows, int n_cols) 
 // ------------------------------------------------------------------- residualise + PCA
 int cna_resid_apply(cna_ctx* c, const double* M, int center) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_resid_apply");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   const int Nx = c->Nx, ldx = c->ldx;
   const int ldb = round_up(Nx, 16);
@@ -1726,6 +1751,7 @@ int cna_resid_apply(cna_ctx* c, const double* M, int center) {
 int cna_resid_lowrank(cna_ctx* c, const double* C, const double* W, int r, int center, int standardize, const double* y,
                       double* max_abs_out) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_resid_lowrank");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (r < 0 || (r > 0 && (!C || !W))) CNA_FAIL(CNA_EINVAL, "cna_resid_lowrank: bad factors");
   const int Nx = c->Nx;
@@ -1771,6 +1797,7 @@ int cna_resid_lowrank(cna_ctx* c, const double* C, const double* W, int r, int c
 int cna_resid_lowrank_bk(cna_ctx* c, const double* C, const double* W, int r, const double* y, double* max_abs_out,
                          const int32_t* batch_codes, int n_batches, double* median_out) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_resid_lowrank_bk");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (r < 0 || (r > 0 && (!C || !W)) || !y || !batch_codes || n_batches < 1 || n_batches > 256 || !median_out)
     CNA_FAIL(CNA_EINVAL, "cna_resid_lowrank_bk: bad arguments");
@@ -1845,6 +1872,7 @@ int cna_select_resid_bk(cna_ctx* c, const double* C, const double* W, int r, con
                         const int32_t* batch_codes, int n_batches, double* median_out, int64_t* n_qc_failed, int64_t* n_zero,
                         int* done) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_select_resid_bk");
   AUTO_FINISH(c);
   if (!done || !median_out || !n_qc_failed || !n_zero || !y || !batch_codes) CNA_FAIL(CNA_EINVAL, "cna_select_resid_bk: null argument");
   *done = 0;
@@ -1934,6 +1962,7 @@ int cna_select_resid_bk(cna_ctx* c, const double* C, const double* W, int r, con
 
 int cna_standardize(cna_ctx* c, int center) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_standardize");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   CNA_TRY(launch_standardize(c, center));
   c->ncorrs_valid = false;
@@ -2017,6 +2046,7 @@ int cna_gram(cna_ctx* c, double* G_out) {
 
 int cna_project(cna_ctx* c, const double* W, int n_w, double* out_local) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_project");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (n_w < 1) CNA_FAIL(CNA_EINVAL, "n_w < 1");
   const int Nx = c->Nx, ldx = c->ldx;
@@ -2040,6 +2070,7 @@ int cna_project(cna_ctx* c, const double* W, int n_w, double* out_local) {
 // cna_fetch_rows(CNA_MAT_PROJ, ...) in whatever row order the caller wants
 int cna_project_keep(cna_ctx* c, const double* W, int n_w) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_project_keep");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (n_w < 1) CNA_FAIL(CNA_EINVAL, "n_w < 1");
   const int Nx = c->Nx, ldx = c->ldx;
@@ -2069,6 +2100,7 @@ int cna_x_identity(cna_ctx* c, int* yes) {
 
 int cna_ncorrs(cna_ctx* c, const double* y, double* out_local, double* max_abs) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_ncorrs");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   void* np = c->ncorrs;
   CNA_TRY(dev_reserve(c, &np, &c->ncorrs_cap, 8 * std::max<int64_t>(c->nx, 1)));
@@ -2167,7 +2199,7 @@ static int ensure_zc(cna_ctx* c, int N, int P, hipStream_t st) {
 // their upload, the threshold counts of the observed coefficients) -- the caller can issue it while
 // the permuted phenotypes are still on their way.  go: the kernel and its reductions; results land in
 // the pinned buffer h_res ([T sums][P*T tails if requested][2T observed counts]) and null_done fires
-// when they are there.  Nothing else may use c->scratch between the two.
+// when they are there.  Nothing else may use c->scratch between the two (NO_NULL_PENDING).
 static int null_local_prepare(cna_ctx* c, int P, const double* edges, int T, int want_tails, const double* thr) {
   if (c->bins_pending) {          // the per-cell counts of the previous pass read its thresholds out of c->scratch (coef_stream)
     HIP_TRY(hipStreamWaitEvent(c->stream, c->bins_copied, 0));
@@ -2228,6 +2260,7 @@ static int null_local_prepare(cna_ctx* c, int P, const double* edges, int T, int
   std::memcpy((char*)c->h_res + stage_off, cuts.data(), 8 * (size_t)T);
   HIP_TRY(hipMemcpyAsync(ed, (char*)c->h_res + stage_off, 8 * T, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->stage_done, c->stream));
+  c->null_stage_off = stage_off;
   c->null_P = P;
   c->null_T = T;
   c->null_has_tails = want_tails;
@@ -2349,26 +2382,32 @@ static int null_local_collect(cna_ctx* c, int64_t* tails_out, int64_t* sums_out,
   if (!c->null_pending) CNA_FAIL(CNA_ESTATE, "no local-null pass pending");
   c->null_pending = 0;
   HIP_TRY(hipEventSynchronize(c->null_done));
-  if (c->null_status_off >= 0 && *(volatile int64_t*)((char*)c->h_res + c->null_status_off) != 0) {
-    // the integer pass gave up (on some rank): the same counts from the f64 kernel, now (the thresholds of the prepare
-    // half are still in the scratch carve: nothing that uses it may run between launch and fetch); the FDR table that
-    // followed the pass on the device was made of the wrong sums -- the per-cell column is looked up again
-    c->null_status_off = -1;
+  const int64_t status_off = c->null_status_off;
+  if (status_off >= 0 && *(volatile int64_t*)((char*)c->h_res + status_off) != 0) {
+    // the integer pass gave up (on some rank): the same counts from the f64 kernel, now.  The FDR table that followed
+    // the pass on the device was made of the wrong sums: fdr_inline is cleared first and the status word's offset only
+    // once the rerun's sums are on the host, so that cna_percell_fdr_copy_early on the helper thread sees either the
+    // raised word or fdr_inline == false (the per-cell column is then looked up again).  The cuts are uploaded again
+    // from the pinned copy the prepare half kept, into the rerun's own carve of c->scratch in stream order (X and Zc
+    // are the launch's: NO_NULL_PENDING).
+    c->fdr_inline = false;
     const int P = c->null_P, T = c->null_T;
+    CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap,
+                        carve_bytes({8 * (int64_t)T, 8 * (int64_t)P * T, 8 * (int64_t)P * T, 8 * (int64_t)T})));
     Carver cv(c->scratch);
     double* ed = cv.take<double>(T);
     unsigned long long* hist = cv.take<unsigned long long>((int64_t)P * T);
     int64_t* tails = cv.take<int64_t>((int64_t)P * T);
     int64_t* sums = cv.take<int64_t>(T);
+    HIP_TRY(hipMemcpyAsync(ed, (char*)c->h_res + c->null_stage_off, 8 * (size_t)T, hipMemcpyHostToDevice, c->stream));
     CNA_TRY(launch_null_local(c, c->zc + c->null_col0, c->zc_ld, P, ed, T, c->null_cut0, c->null_inv_step, c->null_eps, hist, nullptr));
     CNA_TRY(launch_suffix_sum(c, hist, P, T, tails));
     CNA_TRY(launch_tail_sums(c, tails, P, T, sums));
     CNA_TRY(comm_allreduce_i64_sum(c, sums, (size_t)T));
     HIP_TRY(hipMemcpyAsync(c->h_res, sums, 8 * (size_t)T, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->fdr_inline = false;
   }
-  c->null_status_off = -1;
+  c->null_status_off = -1;                               // (after the rerun: see above)
   if (ranks_out || numdet_out) {
     if (!c->null_has_obs) CNA_FAIL(CNA_EINVAL, "the pending pass was launched without thresholds");
     const char* o = (const char*)c->h_res + c->null_obs_off;
@@ -2549,6 +2588,7 @@ int cna_global_test(cna_ctx* c, const double* U, int kmax, const int32_t* ks, in
 int cna_obs_counts(cna_ctx* c, const double* edges, const double* thr, int T, int64_t* ranks_out,
                    int64_t* num_detected_out) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_obs_counts");
   if (!c->ncorrs_valid) CNA_FAIL(CNA_ESTATE, "cna_obs_counts needs cna_ncorrs");
   if (T < 1) CNA_FAIL(CNA_EINVAL, "T < 1");
   double thr0, inv_step;
@@ -2640,8 +2680,10 @@ int cna_percell_fdr_copy_early(cna_ctx* c, double* dst, int64_t n, int nthreads,
   struct Flight { std::atomic<int>& f; Flight(std::atomic<int>& f_) : f(f_) { f.store(1); } ~Flight() { f.store(0); } } flight(c->fdr_early_inflight);
   HIP_TRY(hipEventSynchronize(c->bins_copied));
   HIP_TRY(hipEventSynchronize(c->null_done));
-  if (c->null_status_off >= 0 && *(volatile int64_t*)((char*)c->h_res + c->null_status_off) != 0)
+  const int64_t status_off = c->null_status_off;
+  if (status_off >= 0 && *(volatile int64_t*)((char*)c->h_res + status_off) != 0)
     return 0;                                   // the integer pass gave up: its table is void (cna_null_local_fetch reruns in f64)
+  if (!c->fdr_inline) return 0;                 // ... and the rerun is over already (it clears this flag before the offset)
   if (cna_host_expand_u16(dst, c->h_bins, n, c->h_tab, c->null_T, nthreads) != 0)
     CNA_FAIL(CNA_ESTATE, "cna_percell_fdr_copy_early: expansion failed");
   c->fdr_early_dst = dst;
@@ -2661,6 +2703,7 @@ int cna_percell_fdr_copied_early(cna_ctx* c, int* yes) {
 int cna_percell_fdr_pinned(cna_ctx* c, const double* thr, const double* runmin_fdr, int T, double** coef_ptr,
                            double** fdr_ptr) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_percell_fdr_pinned");
   if (!coef_ptr) CNA_FAIL(CNA_EINVAL, "cna_percell_fdr_pinned: coef_ptr is required");
   const int64_t n_out = c->local_view ? c->n_local : c->n_global;
   CNA_TRY(ensure_cell_pinned(c, n_out));
@@ -2695,6 +2738,7 @@ int cna_percell_fdr_pinned(cna_ctx* c, const double* thr, const double* runmin_f
 int cna_percell_fdr(cna_ctx* c, const double* thr, const double* runmin_fdr, int T, double* coef_out,
                     double* fdr_out) {
   CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_percell_fdr");
   if (!c->ncorrs_valid || !c->x_from_nam) CNA_FAIL(CNA_ESTATE, "cna_percell_fdr needs cna_select + cna_ncorrs");
   const bool want_fdr = fdr_out && thr && runmin_fdr && T > 0;
   double thr0 = 0, inv_step = 0;

@@ -74,7 +74,10 @@ struct cna_ctx {
   int64_t h_res_cap = 0;
   int null_P = 0, null_T = 0, null_has_tails = 0;
   int null_col0 = 0;                   // first column of Zc of the pending pass
-  int64_t null_status_off = -1;        // >= 0: h_res + off holds the integer pass's status word of the pending pass (0: its sums stand)
+  // >= 0: h_res + off holds the integer pass's status word of the pending pass (0: its sums stand); read by the helper
+  // thread's cna_percell_fdr_copy_early, reset only once a rerun is over (null_local_collect)
+  std::atomic<int64_t> null_status_off{-1};
+  int64_t null_stage_off = 0;          // h_res + off: the pinned copy of the prepared pass's exact cuts (its f64 rerun uploads them)
   std::atomic<int> null_pending{0};   // (read by the helper thread's cna_percell_fdr_copy_early, like the four flags below)
   int64_t gram_cap = 0;
   int gram_n = 0;

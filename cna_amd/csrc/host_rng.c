@@ -316,7 +316,7 @@ int cna_host_legacy_randn(uint32_t* key, int* pos, int* has_gauss, double* gauss
     int started[64];
     int nt = host_threads();
     if (nt > 64) nt = 64;
-    if (nt < 1 || pairs < (1 << 18)) nt = 1;         /* (helpers read what ONE producer wrote: slower than none below ~0.25M pairs) */                  /* (25 000 pairs = 50 samples x 1000 permutations split over two to four threads) */
+    if (nt < 1 || pairs < (1 << 18)) nt = 1;         /* (helpers read what ONE producer wrote: slower than none below ~0.25M pairs) */
     for (int t = 0; t < nt; ++t) {
       jobs[t].x1 = ax1; jobs[t].x2 = ax2; jobs[t].r2 = ar2; jobs[t].out = out + done; jobs[t].n_out = n - done;
       jobs[t].a = pairs * t / nt; jobs[t].b = pairs * (t + 1) / nt;
@@ -588,7 +588,6 @@ static int draw_run(const struct draw_req* q) {
 
 /* when the last draw and its follow-up finished (CLOCK_MONOTONIC seconds = std::chrono::steady_clock): stage marks of
  * cna_assoc_finish (cna_assoc_out.t_ms[12], [13]) */
-#include <time.h>
 static double g_draw_times[2];
 static double mono_now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 void cna_host_draw_times(double* out2) { out2[0] = g_draw_times[0]; out2[1] = g_draw_times[1]; }

@@ -680,6 +680,16 @@ def compute_nam_and_reindex(engine, data, y, sid_name, batches, covs, donorids, 
     return (kept, sample_index, colmap, batches, covs, donorids, filter_samples, extra)
 
 
+def _drop_pending_null(engine):
+    """On an error path: the local-null pass the fused selection call may have launched is dropped, else the library
+    refuses the next call's entry points that would disturb it (c_api.hip: NO_NULL_PENDING)."""
+    if getattr(engine, 'null_local_discard', None) is not None:
+        try:
+            engine.null_local_discard()
+        except Exception:               # noqa: BLE001 - the caller gets the error that brought us here
+            pass
+
+
 def association(data, y, sid_name, batches=None, covs=None, donorids=None, ks=None, key_added='coef',
                 max_frac_pcs=0.15, nsteps=None, show_progress=False, allow_low_sample_size=False,
                 return_full=False, ridges=None, engine=None, **kwargs):
@@ -943,7 +953,8 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         null_future.cancel() or null_future.exception()     # do not leave the helper thread running
         if native is not None:
             native.abandon()                                # ... nor the library's draw uncollected (the reference fails before
-        raise                                               #     it seeds, _association.py:15-16: numpy's generator stays as it was)
+        _drop_pending_null(engine)                          #     it seeds, _association.py:15-16: numpy's generator stays as it was)
+        raise                                               # (... nor a local null the fused selection call launched)
     finally:
         engine._on_walk_queued = None
         walk_queued.set()
@@ -954,14 +965,16 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
     nam_epoch = engine.nam_epoch
 
     N = filter_samples.sum()
-    npcs = min(N, max([10] + [int(max_frac_pcs * N)] + [ks if ks is not None else []][0]))
     try:
+        # (raises for a tuple ks, or an ndarray of more than two: the draw and its helper are then stopped below)
+        npcs = min(N, max([10] + [int(max_frac_pcs * N)] + [ks if ks is not None else []][0]))
         res = _resid_run(engine, plan, cell_index, show_progress=show_progress)
     except BaseException:
         null_future.cancel() or null_future.exception()     # do not leave the helper thread running
         if native is not None:
             native.abandon()                                # ... nor the library's draw uncollected (the reference fails before
-        raise                                               #     it seeds, _association.py:15-16: numpy's generator stays as it was)
+        _drop_pending_null(engine)                          #     it seeds, _association.py:15-16: numpy's generator stays as it was)
+        raise                                               # (... nor a local null the fused selection call launched)
 
     _mark('resid queued')
     print('performing association test', file=out)
@@ -1102,10 +1115,7 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         roll_back()
         # the fused selection call may have launched the local null before whatever raised (a `ks` too large for the
         # cohort, a failed draw, an interrupt): collect and drop it, or every later call on this engine finds it pending
-        try:
-            engine.null_local_discard()
-        except Exception:               # noqa: BLE001 - the caller gets the error that brought us here
-            pass
+        _drop_pending_null(engine)
         raise
     if fdr_all is None:
         # upstream has written data.obs[key_added] and then dereferences res.fdrs, which is None when

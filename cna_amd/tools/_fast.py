@@ -93,6 +93,11 @@ def _eligible(data, y, batches, covs, donorids, ks, nsteps, show_progress, engin
     """The cheap part of the shape test (no look at the data)."""
     if not ENABLED or show_progress or batches is not None or donorids is not None:
         return False
+    # ks other than a list: the reference's npcs expression ([10] + [...] + ks, _association.py:207) raises for a tuple
+    # (TypeError) and broadcasts an ndarray (ValueError from max() beyond two entries) on every call -- the general path
+    # evaluates it as the reference does, before anything is queued
+    if ks is not None and not isinstance(ks, list):
+        return False
     # (nsteps=None: the reference's stop rule, _nam.py:59-68 -- evaluated on the device, cna_nam_auto_launch)
     if nsteps is not None and (isinstance(nsteps, bool) or not isinstance(nsteps, (int, np.integer)) or not 1 <= nsteps <= 15):
         return False

@@ -402,3 +402,73 @@ def test_config2_through_the_two_call_path(eng, fast):
                fdrs=dict(threshold=res.fdrs.threshold.values, fdr=res.fdrs.fdr.values, num_detected=res.fdrs.num_detected.values),
                fdr_5p_t=res.fdr_5p_t, fdr_10p_t=res.fdr_10p_t)
     assert_matches_config2(out, z, 1e-5, obs=dict(coef=data.obs['coef'].values, coef_fdr=data.obs['coef_fdr'].values))
+
+
+def _reference_npcs_error(ks, N, max_frac_pcs=0.15):
+    """What the reference's npcs expression (_association.py:207) raises for this ks, evaluated by itself -> (type, text)
+    or None."""
+    try:
+        min(N, max([10] + [int(max_frac_pcs * N)] + [ks if ks is not None else []][0]))
+    except Exception as exc:                   # noqa: BLE001
+        return type(exc), str(exc)
+    return None
+
+
+@pytest.mark.parametrize('return_full', [False, True])
+@pytest.mark.parametrize('ks', [(2, 3), np.array([2, 3, 4]), np.array([2, 3]), [2, 3]],
+                         ids=['tuple', 'ndarray3', 'ndarray2', 'list'])
+def test_ks_types_through_both_paths(eng, fast, ks, return_full):
+    """ks as a tuple, an ndarray or a list, with and without return_full: the two-call path and the general path raise
+    the same exception with the same text, or return the same result.  The reference's npcs expression decides: a tuple
+    is a TypeError, an ndarray of three a ValueError; after a raise data.obs is as it was and the next call on the engine
+    returns what it returned before."""
+    import cna_amd as cna
+    N = 30
+    data, meta = _synthetic(6000, N, seed=23)
+    kw = dict(nsteps=2, Nnull=100, seed=6, engine=eng)
+    expect = _reference_npcs_error(ks, N)
+    assert (expect is not None) == (isinstance(ks, tuple) or (isinstance(ks, np.ndarray) and len(ks) > 2))
+    if isinstance(ks, tuple):
+        assert expect[0] is TypeError
+    elif expect is not None:
+        assert expect[0] is ValueError
+    fast.ENABLED = True
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        p0 = cna.tl.association(data, meta['y'], 'id', **kw)
+    before = {k: data.obs[k].values.copy() for k in ('coef', 'coef_fdr')}
+    out = {}
+    for on in (False, True):
+        fast.ENABLED = on
+        taken0 = fast.stats['taken']
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            try:
+                res = cna.tl.association(data, meta['y'], 'id', ks=ks, return_full=return_full, **kw)
+                err = None
+            except Exception as exc:           # noqa: BLE001
+                res, err = None, exc
+        if expect is not None:
+            assert err is not None and (type(err), str(err)) == expect, (on, err)
+            for k, v in before.items():
+                np.testing.assert_array_equal(data.obs[k].values, v)
+            assert fast.stats['taken'] == taken0
+        else:
+            assert err is None, repr(err)
+            assert fast.stats['taken'] == taken0 + (1 if on and isinstance(ks, list) else 0)
+            if return_full:
+                res.materialize()
+            out[on] = (res, {k: data.obs[k].values.copy() for k in ('coef', 'coef_fdr')})
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            assert cna.tl.association(data, meta['y'], 'id', **kw) == p0
+        for k, v in before.items():
+            np.testing.assert_array_equal(data.obs[k].values, v)
+    if expect is None:
+        (a, oa), (b, ob) = out[False], out[True]
+        if return_full:
+            same_results(a, b)
+        else:
+            assert a == b
+        for k in oa:
+            np.testing.assert_array_equal(oa[k], ob[k])

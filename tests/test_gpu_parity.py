@@ -881,9 +881,21 @@ def test_fdr_column_copied_by_the_helper_thread_equals_the_late_copy(eng, monkey
         out.setdefault(early, []).append((res.p, data.obs['coef'].values.copy(), data.obs['coef_fdr'].values.copy(),
                                           res.fdrs.fdr.values.copy()))
     assert taken == [True, True], taken                    # asked twice (the early runs), served from the helper's copy
+    # ... and an early run whose integer local null gives up (CNA_I8_QCAP): the table that followed it on the device is
+    # void, so the helper's copy must not be served -- the fetch reruns the pass in f64 and the column is looked up again
+    monkeypatch.setattr(A, '_EARLY_FDR', True)
+    monkeypatch.setenv('CNA_I8_QCAP', '8')
+    for key in ('coef', 'coef_fdr'):
+        del data.obs[key]
+    res = cna.tl.association(data, meta['y'], 'id', engine=eng, return_full=True, **kw)
+    monkeypatch.delenv('CNA_I8_QCAP')
+    assert eng.null_local_i8_stats()[2]                     # the rerun really ran
+    assert taken[:2] == [True, True] and True not in taken[2:], taken   # (asked only when the helper reports a copy)
+    assert not real()                                       # the helper's copy of the void table was not served
+    out['gave_up'] = [(res.p, data.obs['coef'].values.copy(), data.obs['coef_fdr'].values.copy(), res.fdrs.fdr.values.copy())]
     p0, c0, f0, t0 = out[False][0]
     assert (f0 < 1).any() and np.isfinite(f0).all()
-    for p1, c1, f1, t1 in out[True]:
+    for p1, c1, f1, t1 in out[True] + out['gave_up']:
         assert p1 == p0
         np.testing.assert_array_equal(c1, c0)
         np.testing.assert_array_equal(f1, f0)

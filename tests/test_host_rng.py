@@ -63,6 +63,46 @@ def test_legacy_randn_on_several_threads_is_numpys_stream(threads):
         _stats._threads_set = False
 
 
+def test_legacy_randn_block_parallel_fuzz():
+    """300 seeded cases of the block-parallel stream: 2 .. 16 threads, random starting positions in the block (odd word
+    counts included), a cached gauss in a third of them, counts from just above the threaded cut-off (8192 pairs) to a
+    few blocks per thread.  Values and generator state bit for bit, and numpy's next draws unchanged."""
+    from cna_amd import _ffi
+    lib = _ffi.load()
+    rs = np.random.RandomState(2024)
+    _stats._threads_set = True
+    try:
+        for case in range(300):
+            threads = int(rs.randint(2, 17))
+            lib.cna_host_set_threads(threads)
+            seed = int(rs.randint(0, 2 ** 31))
+            n = int(rs.randint(2 * 8192, 2 * 8192 + 60000))
+            pre_words = int(rs.randint(0, 2 * 624))           # 32-bit words consumed before the draw
+            gauss = rs.rand() < 1 / 3
+            np.random.seed(seed)
+            if pre_words // 2:
+                np.random.random_sample(pre_words // 2)           # two words each
+            if pre_words % 2:
+                np.random.randint(0, 2 ** 31, dtype=np.int64)     # one word: leaves an odd position
+            if gauss:
+                np.random.randn(1)                                # caches the second value of a pair
+            start = np.random.get_state()
+            assert bool(start[3]) == gauss
+            ref = np.random.randn(n)
+            ref_state = np.random.get_state()
+            ref_next = np.random.randn(3), np.random.randint(0, 1000, 4)
+            np.random.set_state(start)
+            got = _stats.legacy_randn(1, n).ravel().copy()
+            where = (case, threads, seed, n, pre_words, gauss)
+            assert np.array_equal(got.view(np.uint64), ref.view(np.uint64)), where
+            assert _same_state(np.random.get_state(), ref_state), where
+            nxt = np.random.randn(3), np.random.randint(0, 1000, 4)
+            assert all(np.array_equal(u, v) for u, v in zip(nxt, ref_next)), where
+    finally:
+        lib.cna_host_set_threads(1)
+        _stats._threads_set = False
+
+
 def test_permutation_draws_match_plain_numpy(monkeypatch):
     """conditional_permutation / grouplevel_permutation through the fast stream == through np.random.randn."""
     rs = np.random.RandomState(3)
