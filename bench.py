@@ -2,7 +2,7 @@
 """Headline benchmark: cells*permutations / second of an end-to-end ``cna.tl.association``
 (BASELINE.json metric) on synthetic data, HIP path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C3|C2|C5] [--scaling strong|weak] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C3|C2|C5] [--scaling strong|weak] [--dump-outputs DIR] [--full]
 
 A *step* is one full association() call -- NAM diffusion (3 steps) -> QC/selection ->
 residualisation -> Gram/SVD -> global permutation test -> fused local null + FDRs ->
@@ -16,15 +16,21 @@ Workload: BASELINE.json configs[3] ("C4": 2M cells x 200 samples, k=30, nsteps=3
 largest configuration -- it fits one MI355X (~20 GB of 288 GB).  With N > 1 ranks (one per GPU; launched
 by torch.distributed.run, or self-spawned when `--gpus N` is given to a plain `python bench.py`) the
 SAME 2M x 200 problem is sharded over the ranks by row blocks of cells (strong scaling, BASELINE.json's
-"sharded over 8 x MI355X"); `--scaling weak` keeps the per-GPU block fixed instead.  At N = 1 two more
-lines ride along in the same JSON object (`other_configs`): configs[4] ("C5": C4 + 5 covariates, Nnull = 10000),
-configs[2] ("C3", 1M x 100), configs[1] ("C2", 200k x 50), two reference call shapes at C3 and "C4_block8" (250k x 200: one
-rank's share of C4 on eight GPUs as a problem of its own -- the input of DESIGN.md 7's scaling estimate).
+"sharded over 8 x MI355X"); `--scaling weak` keeps the per-GPU block fixed instead.
 
-Prints ONE JSON line on rank 0 (see the repo's bench contract) with two extra objects:
-  roofline     for the kernel that dominates the timed region (HIP-event timed in this run)
-  cpu_baseline oracle/reference_cost.py (the reference's own sequence of library calls, Python loops
-               included) timed here on a bounded sample of the same workload (N = 1 only)
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: nothing else.
+Everything else the bench measures is behind `--full`:
+  - a second loop of the same steps with every kernel group timed: the per-kernel table, `gpu_kernel_ms_per_step`,
+    `host_ms_per_step` and, with N > 1 ranks, `ranks` (what a rank's step is made of);
+  - at N = 1 more lines in the same JSON object (`other_configs`): configs[4] ("C5": C4 + 5 covariates, Nnull = 10000),
+    configs[2] ("C3", 1M x 100), configs[1] ("C2", 200k x 50), two reference call shapes at C3, "C4_block8" (250k x 200:
+    one rank's share of C4 on eight GPUs as a problem of its own -- the input of DESIGN.md 7's scaling estimate) and the
+    opt-in variants of WORKLOADS; at N > 1 the weak-scaling triple `C4_block8_weak`;
+  - cpu_baseline: oracle/reference_cost.py (the reference's own sequence of library calls, Python loops included) timed
+    here on a bounded sample of the same workload, and on the full C2 (and C3) workloads (N = 1 only).
+
+Prints ONE JSON line on rank 0 (see the repo's bench contract) with `roofline` for the kernel that dominates the timed
+region (HIP-event timed in this run: in a plain run, among the walk kernels the timed steps carry events around).
 """
 import argparse
 import json
@@ -205,7 +211,9 @@ class stdout_to_stderr:
 def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dataset=None, keep_outputs=False):
     """Generate the dataset of `name`, run the cold call, warm up, time `steps` calls.  Returns a dict of
     raw measurements (rank 0 fills the JSON from it); with `keep_outputs`, `outputs` holds what the caller of the
-    timed path has after its last timed step (see dump_outputs)."""
+    timed path has after its last timed step (see dump_outputs).  With `want_kernels` (--full) the same steps run
+    once more with every kernel group timed, for the per-kernel table and the per-rank decomposition of a step;
+    without it the kernel figures are those of the timed steps alone (the walk kernels and the communication spans)."""
     import warnings
     import cna_amd as cna
     from cna_amd import synth
@@ -287,7 +295,7 @@ def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dat
 
     # The timed steps carry HIP events around the walk kernels (the dominant kernel of every configuration: `roofline`) and
     # the communication spans only; the per-kernel table comes from a second loop of the same steps with every kernel
-    # group timed -- two event records per group are ~0.1 ms of host time per analysis, 8 % of the 200 000-cell one.
+    # group timed (--full) -- two event records per group are ~0.1 ms of host time per analysis, 8 % of the 200 000-cell one.
     eng.prof_reset()
     eng.prof_enable(True, walk_only=True)
     sync()
@@ -304,34 +312,40 @@ def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dat
                        coef_fdr=np.array(data.obs['coef_fdr'].values, dtype=np.float64))
     eng.prof_enable(False)
     prof_timed = eng.prof()
-    eng.prof_reset()
-    eng.prof_enable(True)
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        cna.tl.association(data, y, 'id', **kw)
-    sync()
-    dt_all_spans = time.perf_counter() - t0
-    eng.prof_enable(False)
-    prof = eng.prof()
-    prof.update(prof_timed)                        # (the walk and the communication: as measured in the timed steps)
+    prof, dt_all_spans = dict(prof_timed), None
+    if want_kernels:
+        eng.prof_reset()
+        eng.prof_enable(True)
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            cna.tl.association(data, y, 'id', **kw)
+        sync()
+        dt_all_spans = time.perf_counter() - t0
+        eng.prof_enable(False)
+        prof = eng.prof()
+        prof.update(prof_timed)                    # (the walk and the communication: as measured in the timed steps)
     dt_local = dt
     if world > 1 or args.force_dist:
         dt = dist.max_over_ranks(dt)               # the slowest rank's clock
     assert p_first == p_last
     # what a rank's step is made of, from every rank (N > 1: so that a scaling curve explains itself): HIP-event times of
     # its compute kernels, of the main communicator's collectives, of the halo exchange and of the main stream's wait for
-    # it, its own wall clock -- microseconds per step, gathered through the library's communicator
+    # it, its own wall clock -- microseconds per step, gathered through the library's communicator (--full: it needs every
+    # kernel group timed)
     comm_keys = ('rccl', 'halo_exchange', 'halo_wait')
     side_keys = ('condition', 'global_test')       # second stream, beside the main one
-    mine = dict(wall_ms=dt_local / steps * 1e3,
-                kernel_ms=sum(ms for k_, (ms, _) in prof.items() if k_ not in comm_keys + side_keys) / steps,
-                allreduce_ms=prof.get('rccl', (0.0, 0))[0] / steps,
-                halo_exchange_ms=prof.get('halo_exchange', (0.0, 0))[0] / steps,
-                halo_wait_ms=prof.get('halo_wait', (0.0, 0))[0] / steps)
-    mine['host_ms'] = mine['wall_ms'] - mine['kernel_ms'] - mine['allreduce_ms'] - mine['halo_wait_ms']
-    rank_keys = sorted(mine)
-    per_rank = eng.allgather_fixed([int(round(mine[k_] * 1e3)) for k_ in rank_keys]).astype(np.float64) * 1e-3
+    per_rank = None
+    if want_kernels:
+        mine = dict(wall_ms=dt_local / steps * 1e3,
+                    kernel_ms=sum(ms for k_, (ms, _) in prof.items() if k_ not in comm_keys + side_keys) / steps,
+                    allreduce_ms=prof.get('rccl', (0.0, 0))[0] / steps,
+                    halo_exchange_ms=prof.get('halo_exchange', (0.0, 0))[0] / steps,
+                    halo_wait_ms=prof.get('halo_wait', (0.0, 0))[0] / steps)
+        mine['host_ms'] = mine['wall_ms'] - mine['kernel_ms'] - mine['allreduce_ms'] - mine['halo_wait_ms']
+        rank_keys = sorted(mine)
+        gathered = eng.allgather_fixed([int(round(mine[k_] * 1e3)) for k_ in rank_keys]).astype(np.float64) * 1e-3
+        per_rank = {k_: [round(float(v), 3) for v in gathered[:, i]] for i, k_ in enumerate(rank_keys)}
 
     if args.profile_host and rank == 0:
         import cProfile
@@ -360,7 +374,7 @@ def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dat
     return dict(name=name, n=n, N=N, k=k, nsteps=nsteps, Nnull=Nnull, n_covs=n_covs, n_batches=n_batches, nnz=nnz, wA=wA, dt=dt, t_cold=t_cold, i8=i8,
                 t_gen=t_gen, prof=prof, dt_all_spans=dt_all_spans, p=p_last, t_adopt=t_adopt, n_loc=n_loc, nnz_loc=nnz_loc, halo=getattr(eng, 'halo', None),
                 sharded_inputs=sharded_inputs, data=data, meta=meta, kw=kw, steps=steps, warmup=warmup, comm=eng.comm_info(),
-                per_rank={k_: [round(float(v), 3) for v in per_rank[:, i]] for i, k_ in enumerate(rank_keys)}, pinned=pinned,
+                per_rank=per_rank, every_kernel_timed=bool(want_kernels), pinned=pinned,
                 two_call_path=_two_call_stats(),
                 halo_comm=getattr(eng, 'halo_comm', False), dev_bytes=int(eng.device_bytes()),
                 state_f32=bool(WORKLOAD_OPTS.get(name, {}).get('state_f32')), outputs=outputs)
@@ -444,9 +458,10 @@ def kernel_table(m, world):
             deg = m['nnz_loc'] / m['n_loc']
             pairs = min(64.0, m['N'] * (1.0 - (1.0 - 1.0 / m['N']) ** (deg + 1.0)))
             work = work - 8 * m['n_loc'] * m['N'] + m['n_loc'] * (16.0 * pairs + 1.0)
-        if name == 'nam_step' and 'select' not in m['prof'] and m['N'] > 64:
+        if name == 'nam_step' and 'select' not in m['prof'] and m['N'] > 64 and m.get('every_kernel_timed', True):
             # the last step also did the selection pass (diffuse.hip:select_tail): it writes X instead of the NAM (same
             # bytes) plus what that pass adds -- three digit planes of 32 ceil(N/32) bytes, coefficient, row scale
+            # (a plain run does not time `select`, so it cannot tell: see summary)
             work += m['n_loc'] * (3 * 32 * ((m['N'] + 31) // 32) + 24)
         if name == 'gram' and cnt > m['steps']:
             # the product ran range by range under the walk's last step (c_api.hip:ranged_last_step): a launch covers
@@ -495,6 +510,8 @@ def summary(m, world, steps):
         # the same launch priced on SURVEY 8(d)'s step bytes alone (`frac` also counts what the fused selection pass
         # writes: X instead of the NAM, digit planes, coefficients)
         roofline['frac_step_bytes'] = kd['frac_step_bytes']
+        if not m.get('every_kernel_timed', True):
+            roofline['frac'] = None        # whether the selection pass rode along shows only with every kernel timed (--full)
     if dom == 'nam_step':
         # what the row-gather actually moves, beside the algorithmic bytes the fraction is priced on: every edge fetches
         # its neighbour's 8N-byte state row through the vector L1 (the chip delivers 17-19 TB/s on this
@@ -506,12 +523,15 @@ def summary(m, world, steps):
             roofline['behind_l2_TBps'] = round(traffic / (kd['avg_us'] * 1e-6) / 1e12, 2)
     # (the exchange runs beside the walk on its own stream and `halo_wait` is the main stream standing still: neither is kernel
     # time; the collectives of the main communicator are, as before)
-    gpu_ms = sum(v['total_ms'] for k_, v in kernels.items() if k_ not in ('halo_exchange', 'halo_wait')) / steps
     ms_per_step = m['dt'] / steps * 1e3
+    gpu_ms = host_ms = None
+    if m.get('every_kernel_timed', True):          # (a plain run times the walk kernels and the communication only)
+        gpu_ms = sum(v['total_ms'] for k_, v in kernels.items() if k_ not in ('halo_exchange', 'halo_wait')) / steps
+        gpu_ms, host_ms = round(gpu_ms, 3), round(ms_per_step - gpu_ms, 3)
     return dict(value=round(m['n'] * m['Nnull'] * steps / m['dt'], 1), ms_per_step=round(ms_per_step, 3), roofline=roofline,
-                kernels=kernels, gpu_kernel_ms_per_step=round(gpu_ms, 3),
+                kernels=kernels, gpu_kernel_ms_per_step=gpu_ms,
                 ms_per_step_all_spans=None if m.get('dt_all_spans') is None else round(m['dt_all_spans'] / steps * 1e3, 3),
-                host_ms_per_step=round(ms_per_step - gpu_ms, 3), ranks=ranks_summary(m, world),
+                host_ms_per_step=host_ms, ranks=ranks_summary(m, world) if m.get('per_rank') else None,
                 graph_pinned=m.get('pinned', True), two_call_path=m.get('two_call_path'),
                 cold_first_call=dict(ms=round(m['t_cold'] * 1e3, 1), value=round(m['n'] * m['Nnull'] / m['t_cold'], 1),
                                      call_that_adopts_the_device_order_ms=None if m.get('t_adopt') is None else round(m['t_adopt'] * 1e3, 1),
@@ -710,7 +730,7 @@ def contract_line(d, details_file=None):
     out['kernels_ms_per_step'] = {k_: [round(v['total_ms'] / steps, 3), round(v['launches'] / steps, 2),
                                        v.get('frac_step_bytes', v.get('frac'))] for k_, v in top}
     out['other_configs'] = others
-    out['details'] = os.path.basename(details_file or DETAILS_FILE) + ' (and stderr): per-kernel tables of every configuration'
+    out['details'] = os.path.basename(details_file or DETAILS_FILE) + ' (and stderr): everything this run measured, per-kernel tables included'
     line = json.dumps(out, separators=(',', ':'))
     assert '\n' not in line
     return line
@@ -725,13 +745,18 @@ def main():
     ap.add_argument('--scaling', default='strong', choices=['strong', 'weak'],
                     help='N>1: strong = the same total problem sharded over the ranks (default, BASELINE configs[3]); '
                          'weak = the workload size PER GPU')
-    ap.add_argument('--no-extra', action='store_true', help='N=1: skip the additional C5, C3 and C2 lines')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the per-kernel table and per-rank decomposition (a second loop of the same '
+                         'steps with every kernel group timed), the other configurations (N=1: C5, C3, C2, ...; N>1: the '
+                         'weak-scaling triple) and the reference-cost CPU baselines.  Without it a run sets up, warms up, '
+                         'times the steps, writes --dump-outputs and prints the line')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip the other configurations')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the reference-cost CPU baselines')
     ap.add_argument('--cpu-sample-cells', type=int, default=150_000)
     ap.add_argument('--no-cpu-c2-full', action='store_true',
-                    help='N=1: skip the reference-cost CPU run of the FULL C2 workload (~1-2 min of host time)')
+                    help='--full, N=1: skip the reference-cost CPU run of the FULL C2 workload (~1-2 min of host time)')
     ap.add_argument('--cpu-full', default='auto',
-                    help='N=1: BASELINE configurations whose FULL workload the reference-cost CPU path runs (C2, C3).  auto: C2, '
+                    help='--full, N=1: BASELINE configurations whose FULL workload the reference-cost CPU path runs (C2, C3).  auto: C2, '
                          'and C3 as well (the "HBM roofline run": ~100 s of host time, ~30 GB) when the host allows it (>= 16 usable cores, >= 64 GB free)')
     ap.add_argument('--details', default=DETAILS_FILE, help='where the full per-kernel tables go (JSON)')
     ap.add_argument('--profile-host', default=None, help='write a cProfile of 3 extra steps to this file')
@@ -800,13 +825,14 @@ def main():
 
     steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.workload][0]
     warmup = args.warmup if args.warmup is not None else DEFAULT_STEPS[args.workload][1]
-    m = time_workload(args.workload, args, rank, world, steps, warmup, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    m = time_workload(args.workload, args, rank, world, steps, warmup, want_kernels=args.full,
+                      keep_outputs=bool(args.dump_outputs) and rank == 0)
     if args.dump_outputs and rank == 0:
         written = dump_outputs(args.dump_outputs, m.pop('outputs'))
         print('bench.py: wrote %s to %s' % (json.dumps(written), args.dump_outputs), file=sys.stderr)
     eng = get_engine()
     weak = None
-    if world > 1 and args.scaling == 'strong' and args.workload == 'C4' and not args.no_extra:
+    if args.full and world > 1 and args.scaling == 'strong' and args.workload == 'C4' and not args.no_extra:
         # the second triple of an N > 1 line: WEAK scaling -- 250 000 cells x 200 samples per rank (a rank's block of C4
         # on eight GPUs), so that one run shows both what a fixed problem gains from N GPUs and what a fixed block costs
         # beside N - 1 others (every rank takes part; rank 0 reports)
@@ -844,7 +870,7 @@ def main():
             extra['C4_block8_weak'] = dict(workload=workload_text(weak, world, args), steps=weak['steps'], warmup=weak['warmup'],
                                            scaling='weak', cells=weak['n'], **s_)
             del weak['data'], weak['meta']
-    if world == 1 and not args.no_extra and args.workload in ('C4', 'C2'):
+    if args.full and world == 1 and not args.no_extra and args.workload in ('C4', 'C2'):
         # the same steps as a drop-in caller gets them: no engine.pin_graph (same dataset object, resident graph)
         uname = args.workload + '_unpinned'
         st_, wu_ = DEFAULT_STEPS[uname]
@@ -856,12 +882,12 @@ def main():
             extra[uname] = dict(error=repr(e))
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_reference_cost(synth, min(args.cpu_sample_cells, m['n']), m['N'], m['k'], m['nsteps'], m['Nnull'], m['n_covs'],
                                  extrapolate_to=m['n'])
     del m['data'], m['meta']
 
-    if world == 1 and not args.no_extra and args.workload == 'C4':
+    if args.full and world == 1 and not args.no_extra and args.workload == 'C4':
         for name in ('C5', 'C3', 'C2', 'C3_default_nsteps', 'C3_covs_batches', 'C4_block8', 'C4_state_f32', 'C3_state_f32',
                      'C2_draw_memo', 'C4_block8_draw_memo'):
             st_, wu_ = DEFAULT_STEPS[name]
@@ -875,7 +901,7 @@ def main():
 
     cpu_c2 = None
     cpu_full = {}
-    if world == 1 and not args.no_cpu_baseline and not args.no_cpu_c2_full:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.no_cpu_c2_full:
         # BASELINE.md 3 asks for the CPU path on a BASELINE configuration in full, in the same run: configs[1] (C2:
         # 200k x 50, nsteps 3, Nnull 1000), no sampling, no extrapolation -- beside this run's GPU time of the same
         # configuration.  (--cpu-full C2,C3 adds configs[2]: minutes of host time and ~30 GB, not in the default run.)

@@ -7,6 +7,8 @@ import json
 import os
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -120,3 +122,92 @@ def test_transport_lines_of_an_rccl_log_are_counted(tmp_path, monkeypatch):
                    'host:1:1 [0] NCCL INFO comm 0x1 rank 0 nranks 2 - Init COMPLETE\n')
     monkeypatch.setenv('CNA_BENCH_NCCL_LOG', str(log))
     assert bench.rccl_transport(0) == {'P2P/IPC': 2, 'NET': 1, 'SHM/direct': 1}
+
+
+WALK = ('nam_first', 'nam_step', 'nam_step_sparse')
+
+
+def plain_measurement(name, steps):
+    """What time_workload returns without want_kernels: the timed steps' own events (walk kernels) and no per-rank table."""
+    m = stub_measurement(name, steps)
+    m['prof'] = {k_: v for k_, v in m['prof'].items() if k_ in WALK}
+    m.update(per_rank=None, every_kernel_timed=False, dt_all_spans=None)
+    return m
+
+
+def test_plain_line_keeps_the_headline_and_the_walk_roofline():
+    args = argparse.Namespace(scaling='strong', partition='populations', comm='rccl', details=None, force_dist=False)
+    m = plain_measurement('C4', 20)
+    main_sum = bench.summary(m, 1, 20)
+    d = json.loads(bench.contract_line(bench.assemble_details(m, main_sum, None, None, {}, 1, 20, 5, args)))
+    full = json.loads(build_line()[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'n_gpus'):
+        assert d[key] == full[key], key
+    assert d['config']['p_value'] == full['config']['p_value']
+    # the walk step dominates: timed in the timed steps themselves.  What the fused selection pass adds to it is known only
+    # when `select` is timed as well (--full)
+    assert d['roofline'].pop('frac_fused') is None and full['roofline'].pop('frac_fused') is not None
+    assert d['roofline'] == full['roofline']
+    assert d['gpu_kernel_ms_per_step'] is None and d['host_ms_per_step'] is None     # they need every kernel timed
+    assert set(d['kernels_ms_per_step']) == set(WALK)
+    assert d['cpu_baseline'] is None and d['other_configs'] == {} and 'ranks' not in d
+    mr = plain_measurement('C4', 20)
+    assert bench.summary(mr, 8, 20)['ranks'] is None
+
+
+class _Engine:
+    def close(self):
+        pass
+
+
+def _run_main(monkeypatch, tmp_path, argv):
+    """bench.main() with the device work stubbed out: which workloads it times, with which options, and what it prints."""
+    import cna_amd
+    import cna_amd.engine
+    calls = []
+
+    def time_workload(name, args, rank, world, steps, warmup, want_kernels=True, dataset=None, keep_outputs=False):
+        calls.append((name, bool(want_kernels)))
+        m = stub_measurement(name, steps) if want_kernels else plain_measurement(name, steps)
+        m.update(data=None, meta=None, steps=steps, warmup=warmup, halo=None, sharded_inputs=False, comm=('none', 1))
+        if keep_outputs:
+            m['outputs'] = dict(p=np.array([m['p']]), coef=np.zeros(4), coef_fdr=np.ones(4))
+        return m
+
+    def cpu_reference_cost(synth, ns, *a, **kw):
+        calls.append(('cpu', ns))
+        return dict(value=1.0, unit='cell*perm/s', cores=16, kind='port', mode='reference-cost', seconds=1.0, p_value=0.5,
+                    stages_s={}, sample_short='s')
+
+    monkeypatch.setattr(bench, 'time_workload', time_workload)
+    monkeypatch.setattr(bench, 'cpu_reference_cost', cpu_reference_cost)
+    monkeypatch.setattr(cna_amd, 'tune_host_allocator', lambda: True)
+    monkeypatch.setattr(cna_amd.engine, 'get_engine', lambda: _Engine())
+    for k_ in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
+        monkeypatch.delenv(k_, raising=False)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--details', str(tmp_path / 'details.json')] + argv)
+    bench.main()
+    return calls
+
+
+def test_a_plain_run_times_the_headline_workload_alone(monkeypatch, tmp_path, capsys):
+    calls = _run_main(monkeypatch, tmp_path, ['--gpus', '1', '--steps', '3', '--warmup', '2',
+                                              '--dump-outputs', str(tmp_path / 'dump')])
+    assert calls == [('C4', False)]
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line['steps'] == 3 and line['warmup'] == 2 and line['metric'] == bench.METRIC and line['ms_per_step'] > 0
+    assert line['cpu_baseline'] is None and line['other_configs'] == {}
+    assert sorted(os.listdir(tmp_path / 'dump')) == ['coef.npy', 'coef_fdr.npy', 'p.npy']
+
+
+def test_full_runs_everything_else(monkeypatch, tmp_path, capsys):
+    calls = _run_main(monkeypatch, tmp_path, ['--gpus', '1', '--full'])
+    assert calls[0] == ('C4', True) and all(w for _, w in calls if _ != 'cpu')
+    timed = [c[0] for c in calls if c[0] != 'cpu']
+    assert set(timed) == {'C4', 'C4_unpinned', 'C5', 'C3', 'C2', 'C3_default_nsteps', 'C3_covs_batches', 'C4_block8',
+                          'C4_state_f32', 'C3_state_f32', 'C2_draw_memo', 'C4_block8_draw_memo'}
+    cpu = [c[1] for c in calls if c[0] == 'cpu']
+    assert cpu[0] == 150_000 and bench.WORKLOADS['C2'][0] in cpu[1:]
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line['cpu_baseline']['value'] == 1.0 and line['cpu_baseline_C2_full'] and line['gpu_kernel_ms_per_step'] > 0
+    assert len(line['other_configs']) == 11

@@ -4,7 +4,7 @@ out=$1; wl=$2; shift 2
 mkdir -p "$(dirname "$out")"
 for cfg in "$@"; do
   echo "## $cfg" >> "$out"
-  env $cfg python bench.py --workload "$wl" --no-extra --no-cpu-baseline --steps 20 --warmup 5 2>>"$out.err" | python -c '
+  env $cfg python bench.py --full --workload "$wl" --no-extra --no-cpu-baseline --steps 20 --warmup 5 2>>"$out.err" | python -c '
 import json,sys
 d=json.loads(sys.stdin.readline())
 k=d["kernels"]

@@ -1,4 +1,4 @@
-"""Walk kernels and step time of every configuration of a bench_details.json, one line each (A/B reading aid)."""
+"""Walk kernels and step time of every configuration of a bench_details.json (bench.py --full), one line each (A/B reading aid)."""
 import json
 import sys
 

@@ -5,7 +5,7 @@
 set -u
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof_r06; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-SHORT="--no-cpu-baseline --no-extra --steps 6 --warmup 2"
+SHORT="--full --no-cpu-baseline --no-extra --steps 6 --warmup 2"
 for W in ${WORKLOADS:-C4 C3 C2 C5}; do
   timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o stats_$W -- python $R/bench.py --workload $W $SHORT > $OUT/stats_$W.log 2>&1
   pass() { n=$1; shift; timeout -k 5 400 rocprofv3 --kernel-trace --output-format csv -d $OUT -o ${n}_$W --pmc "$@" -- python $R/bench.py --workload $W $SHORT > $OUT/${n}_$W.log 2>&1 || echo "pass $n $W failed"; }
