@@ -120,11 +120,68 @@ static const char* kKernelNames[CNA_K_COUNT] = {
 // The contract of a pending local-null pass (launched, not yet fetched): should its integer kernel give up, the fetch
 // reruns it in f64 on the X and Zc the launch saw (null_local_collect).  So every entry point that rewrites X or carves
 // c->scratch refuses with CNA_ESTATE until the pass is fetched (or discarded); nothing is queued and no state changes.
-// Entry points on other buffers (Gram, F-tests, the coefficient column, the FDR copy) may run in between.
+// Entry points on other buffers (Gram, F-tests, the coefficient column, the FDR copy) may run in between.  Every writer
+// of X checks in x_begin; the selections that queue work before it (materialising the NAM) check at their top as well.
 #define NO_NULL_PENDING(c, who)                                                                      \
   do {                                                                                               \
-    if ((c)->null_pending) CNA_FAIL(CNA_ESTATE, who ": a local-null pass is still pending: fetch it first"); \
+    if ((c)->null_pending) CNA_FAIL(CNA_ESTATE, std::string(who) + ": a local-null pass is still pending: fetch it first"); \
   } while (0)
+
+// Derived state holds only as long as what it was derived from.  Three nested transitions are the only places that
+// clear it (common.h tags every flag with the one that clears it); they assign fields and nothing else.
+static void void_x(cna_ctx* c) {          // X and everything derived from it
+  c->x_valid = c->x_from_nam = c->x_ident = false;
+  c->ncorrs_valid = c->xq_valid = c->byp_valid = c->gram_pre = c->proj_valid = false;
+  c->gram_n = 0;
+  c->coef_early = false;
+  c->fdr_inline = false;
+}
+static void void_walk(cna_ctx* c) {       // the walk (state, NAM), then X
+  c->t_valid = c->nam_valid = c->nam_lazy = false;
+  c->steps_done = 0;
+  c->t_f32[0] = c->t_f32[1] = false;
+  void_x(c);
+}
+static void void_cells(cna_ctx* c) {      // the cell space the first step reads, then the walk
+  c->cellinfo_valid = false;
+  void_walk(c);
+}
+
+// Every producer of X brackets its work with x_begin (refused while a local-null pass is pending; whatever was derived
+// from the old X goes) and x_commit (the flags the producer vouches for).  A producer that fails in between leaves X
+// invalid.  In place: the shape stays.
+static int x_begin(cna_ctx* c, const char* who) {
+  NO_NULL_PENDING(c, who);
+  void_x(c);
+  return 0;
+}
+static int x_ld(int Nx);
+// ... a new shape: nx rows (the local NAM rows keep_idx[0 .. nx), or every local row when keep_idx is null) x Nx samples
+static int x_begin(cna_ctx* c, const char* who, int64_t nx, int Nx, const int64_t* keep_idx) {
+  CNA_TRY(x_begin(c, who));
+  c->nx = nx;
+  c->Nx = Nx;
+  c->ldx = x_ld(Nx);
+  void* xp = c->X;
+  CNA_TRY(dev_reserve(c, &xp, &c->x_cap, (int64_t)sizeof(double) * std::max<int64_t>(nx, 1) * c->ldx));
+  c->X = (double*)xp;
+  c->keep_idx = nullptr;
+  if (keep_idx) {
+    void* kp = c->keep_store;
+    CNA_TRY(dev_reserve(c, &kp, &c->keep_cap, 8 * std::max<int64_t>(nx, 1)));
+    c->keep_store = (int64_t*)kp;
+    HIP_TRY(hipMemcpyAsync(c->keep_store, keep_idx, 8 * nx, hipMemcpyHostToDevice, c->stream));
+    c->keep_idx = c->keep_store;
+  }
+  return 0;
+}
+static void x_commit(cna_ctx* c, bool from_nam, bool ncorrs, bool xq, bool ident) {
+  c->x_valid = true;
+  c->x_from_nam = from_nam;
+  c->ncorrs_valid = ncorrs;
+  c->xq_valid = xq;
+  c->x_ident = ident;
+}
 
 // scratch layout helper: carve 256-byte aligned pieces out of c->scratch
 struct Carver {
@@ -321,6 +378,7 @@ int cna_graph_upload(cna_ctx* c, int64_t n_global, int64_t row0, int64_t n_local
   if (indptr[0] != 0) CNA_FAIL(CNA_EINVAL, "cna_graph_upload: indptr must be rebased to start at 0");
   const int64_t nnz = indptr[n_local];
   HIP_TRY(hipStreamSynchronize(c->stream));
+  void_cells(c);
   if (c->indptr) dev_free(c, c->indptr, sizeof(int64_t) * (c->n_local + 1));
   if (c->indices) dev_free(c, c->indices, sizeof(int32_t) * c->nnz);
   if (c->data) dev_free(c, c->data, (c->data_f64 ? 8 : 4) * c->nnz);
@@ -350,16 +408,6 @@ int cna_graph_upload(cna_ctx* c, int64_t n_global, int64_t row0, int64_t n_local
   }
   HIP_TRY(hipMemset(c->stat, 0, sizeof(double) * c->n_pad));
   c->have_colsum = false;
-  c->cellinfo_valid = false;
-  c->t_valid = false;
-  c->nam_valid = false; c->nam_lazy = false;
-  c->x_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->ncorrs_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
-  c->steps_done = 0;
   return 0;
 }
 
@@ -407,24 +455,16 @@ int cna_graph_reorder(cna_ctx* c, const int64_t* perm) {
   HIP_TRY(hipMemsetAsync(c->stat, 0, sizeof(double) * c->n_pad, c->stream));
   // everything that hangs on the order of the cells goes, as after an upload; the column sums and the sample codes were
   // permuted with the graph and stay
-  c->cellinfo_valid = false;
-  c->t_valid = false;
-  c->nam_valid = false; c->nam_lazy = false;
-  c->x_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->ncorrs_valid = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
-  c->steps_done = 0;
-  c->t_f32[0] = c->t_f32[1] = false;
+  void_cells(c);
   return 0;
 }
 
 int cna_set_local_view(cna_ctx* c, int on) {
   CHECK_CTX(c);
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if ((on != 0) != c->local_view && c->orig_idx) {      // a cell order belongs to the view it was given in
-    dev_free(c, c->orig_idx, sizeof(int64_t) * c->n_local);
+  if ((on != 0) != c->local_view) {
+    void_x(c);                      // (the per-cell columns derived from X are laid out for the old view)
+    if (c->orig_idx) dev_free(c, c->orig_idx, sizeof(int64_t) * c->n_local);     // a cell order belongs to the view it was given in
     c->orig_idx = nullptr;
   }
   c->local_view = on != 0;
@@ -536,7 +576,7 @@ int cna_set_samples(cna_ctx* c, const int32_t* codes, int n_samples, const doubl
   HIP_TRY(hipMemcpyAsync(c->sid, codes, sizeof(int32_t) * c->n_global, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->counts, counts, sizeof(double) * n_samples, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->cellinfo_valid = false;
+  void_cells(c);
   CNA_TRY(ensure_T(c, c->ld));
   void* nm = c->nam;
   CNA_TRY(dev_reserve(c, &nm, &c->nam_cap, (int64_t)sizeof(double) * std::max<int64_t>(c->n_local, 1) * c->ld));
@@ -544,12 +584,6 @@ int cna_set_samples(cna_ctx* c, const int32_t* codes, int n_samples, const doubl
   c->t_width = c->N;
   c->t_ld = c->ld;
   c->t_cur = 0;
-  c->t_f32[0] = c->t_f32[1] = false;
-  c->steps_done = 0;
-  c->t_valid = false;
-  c->nam_valid = false; c->nam_lazy = false;
-  c->x_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
   CNA_TRY(ensure_sparse_state(c));
   return 0;
 }
@@ -560,16 +594,11 @@ int cna_restart_nam(cna_ctx* c) {
   if (!c->sid || !c->counts) CNA_FAIL(CNA_ESTATE, "cna_restart_nam needs cna_set_samples first");
   // (no wait for the stream here: the new walk is queued behind whatever still runs on it, and ensure_T waits by itself
   // in the one case that needs it, a reallocation -- the wait cost 20-40 us at the front of every call)
+  void_walk(c);
   CNA_TRY(ensure_T(c, c->ld));
   c->t_width = c->N;
   c->t_ld = c->ld;
   c->t_cur = 0;
-  c->t_f32[0] = c->t_f32[1] = false;
-  c->steps_done = 0;
-  c->t_valid = false;
-  c->nam_valid = false; c->nam_lazy = false;
-  c->x_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
   return 0;
 }
 
@@ -586,8 +615,7 @@ static void halo_clear(cna_ctx* c) {
   if (c->t_compact) {          // the state's row space changes: whatever is in it is void
     c->t_compact = false;
     c->t_rows = 0;
-    c->t_valid = false;
-    c->cellinfo_valid = false;
+    void_cells(c);
   }
   if (c->halo_send_idx) dev_free(c, c->halo_send_idx, sizeof(int64_t) * std::max<int64_t>(c->halo_ns, 1));
   if (c->halo_recv_idx) dev_free(c, c->halo_recv_idx, sizeof(int64_t) * std::max<int64_t>(c->halo_nr, 1));
@@ -686,8 +714,7 @@ int cna_set_halo(cna_ctx* c, const int64_t* send_rows, const int64_t* send_count
       }
       c->t_compact = true;
       c->t_rows = c->n_local + nr;
-      c->t_valid = false;
-      c->cellinfo_valid = false;
+      void_cells(c);
       if (c->sid) {                      // (a plan that arrives after cna_set_samples: size the buffers for the new row space)
         CNA_TRY(ensure_T(c, c->ld));
         CNA_TRY(ensure_sparse_state(c));
@@ -749,7 +776,6 @@ int cna_nam_select_hint(cna_ctx* c, const double* y, int n) {
   return 0;
 }
 
-static int x_ld(int Nx);
 // The NAM on the device, for whoever reads it.  A last step that left the selection pass's results instead (see
 // cna_nam_select_hint) is run once more, now for the NAM: its input state is still in T[t_cur] (a step that ends a walk
 // writes no state), so are the pairs of a two-step walk; same kernel, same inputs, same bits as a first run would give.
@@ -766,30 +792,22 @@ static int need_nam(cna_ctx* c) {
   if (!c->nam_valid) CNA_FAIL(CNA_ESTATE, "NAM not available");
   return 0;
 }
-// 1: the launch that follows is to produce the by-product (buffers sized, y and counters on the device); 0: no
+// 1: the launch that follows is to produce the by-product (buffers sized, y and counters on the device); 0: no.  Never
+// while a local-null pass is pending: the by-product rewrites X, which that pass's f64 rerun may still read (the step
+// then writes the NAM, and the next selection makes the same X from it).
 static int arm_select_byproduct(cna_ctx* c) {
   const char* sw = getenv("CNA_WALK_SELECT");              // A/B switch, read at every walk (tests flip it)
   const bool off = sw && atoi(sw) == 0;
   std::vector<double> y;
   y.swap(c->byp_hint);                                  // one-shot
-  if (off || (int)y.size() != c->N || c->t_ld != c->ld || c->t_ld <= 64 || c->N < 2 || c->n_local < 1) return 0;
+  if (off || c->null_pending || (int)y.size() != c->N || c->t_ld != c->ld || c->t_ld <= 64 || c->N < 2 || c->n_local < 1)
+    return 0;
   const int64_t nx = c->n_local;
   const int Nx = c->N;
-  void* xp = c->X;
-  if (dev_reserve(c, &xp, &c->x_cap, (int64_t)sizeof(double) * nx * x_ld(Nx))) return 0;
-  c->X = (double*)xp;
+  if (x_begin(c, "cna_nam_step", nx, Nx, nullptr)) return 0;
   void* np = c->ncorrs;
   if (dev_reserve(c, &np, &c->ncorrs_cap, 8 * nx)) return 0;
   c->ncorrs = (double*)np;
-  c->nx = nx;
-  c->Nx = Nx;
-  c->ldx = x_ld(Nx);
-  c->keep_idx = nullptr;
-  c->x_valid = false;
-  c->ncorrs_valid = false;
-  c->xq_valid = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
   c->byp_with_q = Nx <= 256 && null_i8_enabled();
   if (c->byp_with_q && ensure_xq(c, (Nx + 31) / 32)) return 0;
   if (!c->byp_buf) return 0;
@@ -1265,6 +1283,62 @@ int cna_dense_fetch(cna_ctx* c, double* out) {
 }
 
 // ------------------------------------------------------------------------ QC / select
+// The samples batch by batch: order[boff[b] .. boff[b + 1]) are those of batch b (a code outside [0, n_batches): none)
+static void batch_order(const int32_t* codes, int ncols, int n_batches, std::vector<int32_t>& order, std::vector<int32_t>& boff) {
+  boff.assign(n_batches + 1, 0);
+  for (int s = 0; s < ncols; ++s)
+    if (codes[s] >= 0 && codes[s] < n_batches) boff[codes[s] + 1]++;
+  for (int b = 0; b < n_batches; ++b) boff[b + 1] += boff[b];
+  order.assign(std::max(boff[n_batches], 1), 0);
+  std::vector<int32_t> cur(boff.begin(), boff.end() - 1);
+  for (int s = 0; s < ncols; ++s)
+    if (codes[s] >= 0 && codes[s] < n_batches) order[cur[codes[s]]++] = s;
+}
+
+// W (r x Nx) and C^T (C: Nx x r, row-major) of the projector M = I - C.W to the device, into Wd / Ctd; Ct is the host
+// copy of C^T, kept by the caller until its next wait.  r = 0: nothing is sent.
+static int upload_factors(cna_ctx* c, const double* C, const double* W, int r, int Nx, double* Wd, double* Ctd,
+                          std::vector<double>& Ct) {
+  Ct.assign((size_t)std::max(r, 1) * Nx, 0.0);
+  for (int i = 0; i < Nx; ++i)
+    for (int k = 0; k < r; ++k) Ct[(size_t)k * Nx + i] = C[(size_t)i * r + k];
+  if (r > 0) {
+    HIP_TRY(hipMemcpyAsync(Wd, W, 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(Ctd, Ct.data(), 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
+  }
+  return 0;
+}
+
+// Behind a pass that left the batch kurtosis of X's rows in c->stat: its median formed on the device, then max
+// |coefficient| (*mb) and that median queued for the host -- in *m and *med after the caller's next wait
+static int queue_bk_results(cna_ctx* c, const unsigned long long* mb, double* m, double* med) {
+  const bool sharded = c->nranks > 1 || comm_active(c);
+  unsigned long long* hist = nullptr;
+  CNA_TRY(ensure_auto_state(c, &hist));
+  const size_t sb = (auto_state_bytes() + 255) & ~(size_t)255;
+  HIP_TRY(hipMemsetAsync(c->auto_state, 0, sb, c->stream));
+  CNA_TRY(launch_auto_median(c, c->stat, c->nx, c->auto_state, hist, -1, 0, sharded));
+  HIP_TRY(hipMemcpyAsync(m, mb, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(med, (const char*)c->auto_state + auto_state_result_offset(), 8, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+
+// The operand of launch_xb in c->scratch: ldx x ldb (ldb = ncols rounded up to 16), zero beyond Nx x ncols, where row k
+// holds row k of A (Nx x ncols, row-major), column k of A when `transposed` (A: ncols x Nx), or (A null) of the identity.
+// B is the host copy, kept by the caller until its next wait.
+static int xb_operand(cna_ctx* c, const double* A, int ncols, bool transposed, std::vector<double>& B, int* ldb_out) {
+  const int Nx = c->Nx, ldx = c->ldx;
+  const int ldb = round_up(ncols, 16);
+  B.assign((size_t)ldx * ldb, 0.0);
+  for (int k = 0; k < Nx; ++k)
+    for (int j = 0; j < ncols; ++j)
+      B[(size_t)k * ldb + j] = !A ? (j == k ? 1.0 : 0.0) : transposed ? A[(size_t)j * Nx + k] : A[(size_t)k * ncols + j];
+  CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, (int64_t)sizeof(double) * ldx * ldb));
+  HIP_TRY(hipMemcpyAsync(c->scratch, B.data(), sizeof(double) * ldx * ldb, hipMemcpyHostToDevice, c->stream));
+  *ldb_out = ldb;
+  return 0;
+}
+
 int cna_batch_kurtosis(cna_ctx* c, int which, const int32_t* batch_codes, int n_batches) {
   CHECK_CTX(c);
   NO_NULL_PENDING(c, "cna_batch_kurtosis");
@@ -1284,14 +1358,8 @@ int cna_batch_kurtosis(cna_ctx* c, int which, const int32_t* batch_codes, int n_
     CNA_FAIL(CNA_EINVAL, "bad matrix selector");
   }
   if (n_batches < 1) CNA_FAIL(CNA_EINVAL, "n_batches < 1");
-  std::vector<int32_t> order, boff(n_batches + 1, 0);
-  for (int s = 0; s < ncols; ++s)
-    if (batch_codes[s] >= 0 && batch_codes[s] < n_batches) boff[batch_codes[s] + 1]++;
-  for (int b = 0; b < n_batches; ++b) boff[b + 1] += boff[b];
-  order.resize(std::max(boff[n_batches], 1));
-  std::vector<int32_t> cur(boff.begin(), boff.end() - 1);
-  for (int s = 0; s < ncols; ++s)
-    if (batch_codes[s] >= 0 && batch_codes[s] < n_batches) order[cur[batch_codes[s]]++] = s;
+  std::vector<int32_t> order, boff;
+  batch_order(batch_codes, ncols, n_batches, order, boff);
   CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, carve_bytes({(int64_t)4 * (int64_t)order.size(), 4 * (n_batches + 1)})));
   Carver cv(c->scratch);
   int32_t* order_dev = cv.take<int32_t>(order.size());
@@ -1361,33 +1429,13 @@ int cna_select(cna_ctx* c, const int64_t* keep_idx, int64_t n_keep, const int32_
   const int64_t nx = keep_idx ? n_keep : c->n_local;
   const int Nx = colmap ? n_sel : c->N;
   if (nx < 0 || nx > c->n_local || Nx < 1) CNA_FAIL(CNA_EINVAL, "cna_select: bad sizes");
-  c->nx = nx;
-  c->Nx = Nx;
-  c->ldx = x_ld(Nx);
-  void* xp = c->X;
-  CNA_TRY(dev_reserve(c, &xp, &c->x_cap, (int64_t)sizeof(double) * std::max<int64_t>(nx, 1) * c->ldx));
-  c->X = (double*)xp;
-  if (keep_idx) {
-    void* kp = c->keep_store;
-    CNA_TRY(dev_reserve(c, &kp, &c->keep_cap, 8 * std::max<int64_t>(nx, 1)));
-    c->keep_store = (int64_t*)kp;
-    HIP_TRY(hipMemcpyAsync(c->keep_store, keep_idx, 8 * nx, hipMemcpyHostToDevice, c->stream));
-    c->keep_idx = c->keep_store;
-  } else {
-    c->keep_idx = nullptr;   // identity: every local NAM row
-  }
+  CNA_TRY(x_begin(c, "cna_select", nx, Nx, keep_idx));
   CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, 4 * (int64_t)Nx + 256));
   int32_t* cm = (int32_t*)c->scratch;
   if (colmap) HIP_TRY(hipMemcpyAsync(cm, colmap, 4 * Nx, hipMemcpyHostToDevice, c->stream));
-  int r = launch_select(c, colmap ? cm : nullptr);
-  CNA_TRY(r);
+  CNA_TRY(launch_select(c, colmap ? cm : nullptr));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->x_valid = true;
-  c->x_from_nam = true;
-  c->ncorrs_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, true, false, false, false);
   return 0;
 }
 
@@ -1426,21 +1474,7 @@ int cna_select_checked(cna_ctx* c, const int64_t* keep_idx, int64_t n_keep, cons
   const int64_t nx = keep_idx ? n_keep : c->n_local;
   const int Nx = colmap ? n_sel : c->N;
   if (nx < 0 || nx > c->n_local || Nx < 1) CNA_FAIL(CNA_EINVAL, "cna_select_checked: bad sizes");
-  c->nx = nx;
-  c->Nx = Nx;
-  c->ldx = x_ld(Nx);
-  void* xp = c->X;
-  CNA_TRY(dev_reserve(c, &xp, &c->x_cap, (int64_t)sizeof(double) * std::max<int64_t>(nx, 1) * c->ldx));
-  c->X = (double*)xp;
-  if (keep_idx) {
-    void* kp = c->keep_store;
-    CNA_TRY(dev_reserve(c, &kp, &c->keep_cap, 8 * std::max<int64_t>(nx, 1)));
-    c->keep_store = (int64_t*)kp;
-    HIP_TRY(hipMemcpyAsync(c->keep_store, keep_idx, 8 * nx, hipMemcpyHostToDevice, c->stream));
-    c->keep_idx = c->keep_store;
-  } else {
-    c->keep_idx = nullptr;
-  }
+  CNA_TRY(x_begin(c, "cna_select_checked", nx, Nx, keep_idx));
   CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, carve_bytes({4 * (int64_t)Nx, 8})));
   Carver cv(c->scratch);
   int32_t* cm = cv.take<int32_t>(Nx);
@@ -1452,12 +1486,7 @@ int cna_select_checked(cna_ctx* c, const int64_t* keep_idx, int64_t n_keep, cons
   HIP_TRY(hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (n_zero_out) *n_zero_out = (int64_t)h;
-  c->x_valid = true;
-  c->x_from_nam = true;
-  c->ncorrs_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, true, false, false, false);
   return 0;
 }
 
@@ -1481,28 +1510,12 @@ static int select_standardized_impl(cna_ctx* c, const int64_t* keep_idx, int64_t
   AUTO_FINISH(c);
   if (gram_too) *gram_too = false;
   if (!c->nam_valid && !c->nam_lazy) CNA_FAIL(CNA_ESTATE, "NAM not available");
-  const bool byp_was = c->byp_valid;
-  const bool gram_pre_was = c->gram_pre;
-  c->byp_valid = false;
-  c->gram_pre = false;
   const int64_t nx = keep_idx ? n_keep : c->n_local;
   const int Nx = colmap ? n_sel : c->N;
   if (nx < 0 || nx > c->n_local || Nx < 2) CNA_FAIL(CNA_EINVAL, "cna_select_standardized: bad sizes");
-  c->nx = nx;
-  c->Nx = Nx;
-  c->ldx = x_ld(Nx);
-  void* xp = c->X;
-  CNA_TRY(dev_reserve(c, &xp, &c->x_cap, (int64_t)sizeof(double) * std::max<int64_t>(nx, 1) * c->ldx));
-  c->X = (double*)xp;
-  if (keep_idx) {
-    void* kp = c->keep_store;
-    CNA_TRY(dev_reserve(c, &kp, &c->keep_cap, 8 * std::max<int64_t>(nx, 1)));
-    c->keep_store = (int64_t*)kp;
-    HIP_TRY(hipMemcpyAsync(c->keep_store, keep_idx, 8 * nx, hipMemcpyHostToDevice, c->stream));
-    c->keep_idx = c->keep_store;
-  } else {
-    c->keep_idx = nullptr;
-  }
+  const bool byp_was = c->byp_valid;      // (the walk's by-product and the Gram matrix taken under it: x_begin voids both)
+  const bool gram_pre_was = c->gram_pre;
+  CNA_TRY(x_begin(c, "cna_select_standardized", nx, Nx, keep_idx));
   CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, carve_bytes({4 * (int64_t)Nx, 8 * (int64_t)Nx, 8 * 4099})));
   Carver cv(c->scratch);
   int32_t* cm = cv.take<int32_t>(Nx);
@@ -1518,7 +1531,6 @@ static int select_standardized_impl(cna_ctx* c, const int64_t* keep_idx, int64_t
   }
   const int rk = (c->resid_rk > 0 && c->resid_n == Nx) ? c->resid_rk : 0;     // one-shot: cna_set_resid_factors
   // the rows leave this pass final: their fixed-point digit planes for the integer local null go out with them
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false;
   const bool with_q = y != nullptr && Nx <= 256 && nx > 0 && null_i8_enabled();
   const int KSq = (Nx + 31) / 32;
   if (with_q) CNA_TRY(ensure_xq(c, KSq));
@@ -1592,16 +1604,11 @@ static int select_standardized_impl(cna_ctx* c, const int64_t* keep_idx, int64_t
   }
   if (n_zero_out) *n_zero_out = (int64_t)h;
   if (max_abs_out) *max_abs_out = m;
-  c->x_valid = true;
-  c->x_from_nam = true;
-  c->ncorrs_valid = y != nullptr;     // meaningful only when no cell had zero variance (the caller checks)
-  c->xq_valid = with_q;
-  // X is now the standardised NAM of every cell with the samples in place and nothing regressed out: a function of
-  // the NAM alone, so a further analysis of the resident dataset that asks for the same selection can keep it
-  // (cna_x_identity) and take only its coefficients (cna_ncorrs)
-  c->x_ident = !keep_idx && in_place && rk == 0 && h == 0 && Nx == c->N && nx == c->n_local;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  // (coefficients: meaningful only when no cell had zero variance, the caller checks.)  With ident, X is the standardised
+  // NAM of every cell with the samples in place and nothing regressed out: a function of the NAM alone, so a further
+  // analysis of the resident dataset that asks for the same selection can keep it (cna_x_identity) and take only its
+  // coefficients (cna_ncorrs)
+  x_commit(c, true, y != nullptr, with_q, !keep_idx && in_place && rk == 0 && h == 0 && Nx == c->N && nx == c->n_local);
   if (fused) {                                   // what cna_gram_launch does after its kernels
     CNA_TRY(comm_allreduce_f64_sum(c, c->gram_buf, (size_t)Nx * Nx));
     CNA_TRY(gram_host_finish(c, Nx));
@@ -1701,47 +1708,29 @@ int cna_select_standardized_fused(cna_ctx* c, const int64_t* keep_idx, int64_t n
 
 int cna_upload_x(cna_ctx* c, const double* x_local, int64_t n_rows, int n_cols) {
   CHECK_CTX(c);
-  NO_NULL_PENDING(c, "cna_upload_x");
   if (n_rows < 0 || n_cols < 1 || n_cols > 1024) CNA_FAIL(CNA_EINVAL, "cna_upload_x: bad shape");
-  c->nx = n_rows;
-  c->Nx = n_cols;
-  c->ldx = x_ld(n_cols);
-  void* xp = c->X;
-  CNA_TRY(dev_reserve(c, &xp, &c->x_cap, (int64_t)sizeof(double) * std::max<int64_t>(n_rows, 1) * c->ldx));
-  c->X = (double*)xp;
+  CNA_TRY(x_begin(c, "cna_upload_x", n_rows, n_cols, nullptr));
   HIP_TRY(hipMemsetAsync(c->X, 0, sizeof(double) * std::max<int64_t>(n_rows, 1) * c->ldx, c->stream));
   if (n_rows > 0)
     HIP_TRY(hipMemcpy2DAsync(c->X, sizeof(double) * c->ldx, x_local, sizeof(double) * n_cols,
                              sizeof(double) * n_cols, n_rows, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->keep_idx = nullptr;
-  c->x_valid = true;
-  c->x_from_nam = false;
-  c->ncorrs_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, false, false, false, false);
   return 0;
 }
 
 // ------------------------------------------------------------------- residualise + PCA
 int cna_resid_apply(cna_ctx* c, const double* M, int center) {
   CHECK_CTX(c);
-  NO_NULL_PENDING(c, "cna_resid_apply");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
-  const int Nx = c->Nx, ldx = c->ldx;
-  const int ldb = round_up(Nx, 16);
-  std::vector<double> B((size_t)ldx * ldb, 0.0);
-  for (int k = 0; k < Nx; ++k)
-    for (int j = 0; j < Nx; ++j) B[(size_t)k * ldb + j] = M ? M[(size_t)j * Nx + k] : (j == k ? 1.0 : 0.0);
-  CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, (int64_t)sizeof(double) * ldx * ldb));
-  HIP_TRY(hipMemcpyAsync(c->scratch, B.data(), sizeof(double) * ldx * ldb, hipMemcpyHostToDevice, c->stream));
-  CNA_TRY(launch_xb(c, (const double*)c->scratch, ldb, Nx, center != 0, c->X, ldx));
+  const bool from_nam = c->x_from_nam;
+  CNA_TRY(x_begin(c, "cna_resid_apply"));
+  std::vector<double> B;
+  int ldb;
+  CNA_TRY(xb_operand(c, M, c->Nx, true, B, &ldb));      // M^T
+  CNA_TRY(launch_xb(c, (const double*)c->scratch, ldb, c->Nx, center != 0, c->X, c->ldx));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->ncorrs_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, from_nam, false, false, false);
   return 0;
 }
 
@@ -1751,9 +1740,10 @@ int cna_resid_apply(cna_ctx* c, const double* M, int center) {
 int cna_resid_lowrank(cna_ctx* c, const double* C, const double* W, int r, int center, int standardize, const double* y,
                       double* max_abs_out) {
   CHECK_CTX(c);
-  NO_NULL_PENDING(c, "cna_resid_lowrank");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (r < 0 || (r > 0 && (!C || !W))) CNA_FAIL(CNA_EINVAL, "cna_resid_lowrank: bad factors");
+  const bool from_nam = c->x_from_nam;
+  CNA_TRY(x_begin(c, "cna_resid_lowrank"));
   const int Nx = c->Nx;
   CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, carve_bytes({8 * (int64_t)std::max(r, 1) * Nx, 8 * (int64_t)std::max(r, 1) * Nx, 8 * (int64_t)Nx, 8 * 2049})));
   Carver cv(c->scratch);
@@ -1761,13 +1751,8 @@ int cna_resid_lowrank(cna_ctx* c, const double* C, const double* W, int r, int c
   double* Ctd = cv.take<double>((int64_t)std::max(r, 1) * Nx);
   double* yd = cv.take<double>(Nx);
   unsigned long long* mb = cv.take<unsigned long long>(2049);
-  std::vector<double> Ct((size_t)std::max(r, 1) * Nx, 0.0);
-  for (int i = 0; i < Nx; ++i)
-    for (int k = 0; k < r; ++k) Ct[(size_t)k * Nx + i] = C[(size_t)i * r + k];
-  if (r > 0) {
-    HIP_TRY(hipMemcpyAsync(Wd, W, 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(Ctd, Ct.data(), 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
-  }
+  std::vector<double> Ct;
+  CNA_TRY(upload_factors(c, C, W, r, Nx, Wd, Ctd, Ct));
   if (y) {
     void* np = c->ncorrs;
     CNA_TRY(dev_reserve(c, &np, &c->ncorrs_cap, 8 * std::max<int64_t>(c->nx, 1)));
@@ -1782,10 +1767,7 @@ int cna_resid_lowrank(cna_ctx* c, const double* C, const double* W, int r, int c
   }
   HIP_TRY(hipStreamSynchronize(c->stream));        // Ct is a local
   if (max_abs_out) *max_abs_out = m;
-  c->ncorrs_valid = y != nullptr;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, from_nam, y != nullptr, false, false);
   return 0;
 }
 
@@ -1797,20 +1779,15 @@ int cna_resid_lowrank(cna_ctx* c, const double* C, const double* W, int r, int c
 int cna_resid_lowrank_bk(cna_ctx* c, const double* C, const double* W, int r, const double* y, double* max_abs_out,
                          const int32_t* batch_codes, int n_batches, double* median_out) {
   CHECK_CTX(c);
-  NO_NULL_PENDING(c, "cna_resid_lowrank_bk");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (r < 0 || (r > 0 && (!C || !W)) || !y || !batch_codes || n_batches < 1 || n_batches > 256 || !median_out)
     CNA_FAIL(CNA_EINVAL, "cna_resid_lowrank_bk: bad arguments");
   if (c->nx > c->n_pad) CNA_FAIL(CNA_EINVAL, "X larger than the stat buffer");
+  const bool from_nam = c->x_from_nam;
+  CNA_TRY(x_begin(c, "cna_resid_lowrank_bk"));
   const int Nx = c->Nx;
-  std::vector<int32_t> order, boff(n_batches + 1, 0);
-  for (int s = 0; s < Nx; ++s)
-    if (batch_codes[s] >= 0 && batch_codes[s] < n_batches) boff[batch_codes[s] + 1]++;
-  for (int b = 0; b < n_batches; ++b) boff[b + 1] += boff[b];
-  order.resize(std::max(boff[n_batches], 1));
-  std::vector<int32_t> cur(boff.begin(), boff.end() - 1);
-  for (int s = 0; s < Nx; ++s)
-    if (batch_codes[s] >= 0 && batch_codes[s] < n_batches) order[cur[batch_codes[s]]++] = s;
+  std::vector<int32_t> order, boff;
+  batch_order(batch_codes, Nx, n_batches, order, boff);
   const int64_t rn = 8 * (int64_t)std::max(r, 1) * Nx;
   CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap,
                       carve_bytes({rn, rn, 8 * (int64_t)Nx, 8 * 2049, 4 * (int64_t)order.size(), 4 * (n_batches + 1)})));
@@ -1821,13 +1798,8 @@ int cna_resid_lowrank_bk(cna_ctx* c, const double* C, const double* W, int r, co
   unsigned long long* mb = cv.take<unsigned long long>(2049);
   int32_t* order_dev = cv.take<int32_t>(order.size());
   int32_t* boff_dev = cv.take<int32_t>(n_batches + 1);
-  std::vector<double> Ct((size_t)std::max(r, 1) * Nx, 0.0);
-  for (int i = 0; i < Nx; ++i)
-    for (int k = 0; k < r; ++k) Ct[(size_t)k * Nx + i] = C[(size_t)i * r + k];
-  if (r > 0) {
-    HIP_TRY(hipMemcpyAsync(Wd, W, 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(Ctd, Ct.data(), 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
-  }
+  std::vector<double> Ct;
+  CNA_TRY(upload_factors(c, C, W, r, Nx, Wd, Ctd, Ct));
   void* np = c->ncorrs;
   CNA_TRY(dev_reserve(c, &np, &c->ncorrs_cap, 8 * std::max<int64_t>(c->nx, 1)));
   c->ncorrs = (double*)np;
@@ -1838,22 +1810,12 @@ int cna_resid_lowrank_bk(cna_ctx* c, const double* C, const double* W, int r, co
   c->stat_space = CNA_MAT_X;
   CNA_TRY(comm_allreduce_f64_max(c, (double*)mb, 1));
   // the median of the batch kurtosis, on the device; its result and max |coefficient| come back with one wait
-  const bool sharded = c->nranks > 1 || comm_active(c);
-  unsigned long long* hist = nullptr;
-  CNA_TRY(ensure_auto_state(c, &hist));
-  const size_t sb = (auto_state_bytes() + 255) & ~(size_t)255;
-  HIP_TRY(hipMemsetAsync(c->auto_state, 0, sb, c->stream));
-  CNA_TRY(launch_auto_median(c, c->stat, c->nx, c->auto_state, hist, -1, 0, sharded));
   double m = 0.0, med = 0.0;
-  HIP_TRY(hipMemcpyAsync(&m, mb, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&med, (const char*)c->auto_state + auto_state_result_offset(), 8, hipMemcpyDeviceToHost, c->stream));
+  CNA_TRY(queue_bk_results(c, mb, &m, &med));
   HIP_TRY(hipStreamSynchronize(c->stream));        // (Ct, order, boff are locals)
   if (max_abs_out) *max_abs_out = m;
   *median_out = med;
-  c->ncorrs_valid = true;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, from_nam, true, false, false);
   return 0;
 }
 
@@ -1884,19 +1846,9 @@ int cna_select_resid_bk(cna_ctx* c, const double* C, const double* W, int r, con
   if (c->n_local > c->n_pad) return 0;
   CNA_TRY(need_nam(c));
   CNA_TRY(gram_pre_settle(c));
-  std::vector<int32_t> order(Nx), boff(n_batches + 1, 0);
-  for (int s = 0; s < Nx; ++s) boff[batch_codes[s] + 1]++;
-  for (int b = 0; b < n_batches; ++b) boff[b + 1] += boff[b];
-  std::vector<int32_t> cur(boff.begin(), boff.end() - 1);
-  for (int s = 0; s < Nx; ++s) order[cur[batch_codes[s]]++] = s;
-  c->byp_valid = false; c->gram_pre = false; c->x_ident = false; c->xq_valid = false;
-  c->nx = c->n_local;
-  c->Nx = Nx;
-  c->ldx = x_ld(Nx);
-  c->keep_idx = nullptr;
-  void* xp = c->X;
-  CNA_TRY(dev_reserve(c, &xp, &c->x_cap, (int64_t)sizeof(double) * std::max<int64_t>(c->nx, 1) * c->ldx));
-  c->X = (double*)xp;
+  std::vector<int32_t> order, boff;
+  batch_order(batch_codes, Nx, n_batches, order, boff);
+  CNA_TRY(x_begin(c, "cna_select_resid_bk", c->n_local, Nx, nullptr));
   void* np = c->ncorrs;
   CNA_TRY(dev_reserve(c, &np, &c->ncorrs_cap, 8 * std::max<int64_t>(c->nx, 1)));
   c->ncorrs = (double*)np;
@@ -1910,11 +1862,8 @@ int cna_select_resid_bk(cna_ctx* c, const double* C, const double* W, int r, con
   int32_t* order_dev = cv.take<int32_t>(Nx);
   int32_t* boff_dev = cv.take<int32_t>(n_batches + 1);
   unsigned long long* counters = cv.take<unsigned long long>(2);
-  std::vector<double> Ct((size_t)r * Nx, 0.0);
-  for (int i = 0; i < Nx; ++i)
-    for (int k = 0; k < r; ++k) Ct[(size_t)k * Nx + i] = C[(size_t)i * r + k];
-  HIP_TRY(hipMemcpyAsync(Wd, W, 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(Ctd, Ct.data(), 8 * (size_t)r * Nx, hipMemcpyHostToDevice, c->stream));
+  std::vector<double> Ct;
+  CNA_TRY(upload_factors(c, C, W, r, Nx, Wd, Ctd, Ct));
   HIP_TRY(hipMemcpyAsync(yd, y, 8 * Nx, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(order_dev, order.data(), 4 * (size_t)Nx, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(boff_dev, boff.data(), 4 * (n_batches + 1), hipMemcpyHostToDevice, c->stream));
@@ -1926,49 +1875,35 @@ int cna_select_resid_bk(cna_ctx* c, const double* C, const double* W, int r, con
                           c->stat, counters);
   }
   if (rc < 0) return rc;
-  if (rc == 0) {                                   // (CNA_ROWPASS16=0 or a shape the sixteen-row pass does not take)
+  if (rc == 0) {                                   // (CNA_ROWPASS16=0 or a shape the sixteen-row pass does not take: X stays void)
     HIP_TRY(hipStreamSynchronize(c->stream));      // (the uploads read locals)
-    c->x_valid = false;
     return 0;
   }
   // every cell is a row of X, also where the NAM has padding columns beyond ldx
   c->stat_space = CNA_MAT_X;
   CNA_TRY(comm_allreduce_f64_max(c, (double*)mb, 1));
   CNA_TRY(comm_allreduce_i64_sum(c, (int64_t*)counters, 2));
-  const bool sharded = c->nranks > 1 || comm_active(c);
-  unsigned long long* hist = nullptr;
-  CNA_TRY(ensure_auto_state(c, &hist));
-  const size_t sb = (auto_state_bytes() + 255) & ~(size_t)255;
-  HIP_TRY(hipMemsetAsync(c->auto_state, 0, sb, c->stream));
-  CNA_TRY(launch_auto_median(c, c->stat, c->nx, c->auto_state, hist, -1, 0, sharded));
   double m = 0.0, med = 0.0;
   unsigned long long cnt[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(&m, mb, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&med, (const char*)c->auto_state + auto_state_result_offset(), 8, hipMemcpyDeviceToHost, c->stream));
+  CNA_TRY(queue_bk_results(c, mb, &m, &med));
   HIP_TRY(hipMemcpyAsync(cnt, counters, 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));        // (Ct, order, boff are locals)
   if (max_abs_out) *max_abs_out = m;
   *median_out = med;
   *n_qc_failed = (int64_t)cnt[0];
   *n_zero = (int64_t)cnt[1];
-  c->x_valid = true;
-  c->x_from_nam = true;
-  c->ncorrs_valid = true;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, true, true, false, false);
   *done = 1;
   return 0;
 }
 
 int cna_standardize(cna_ctx* c, int center) {
   CHECK_CTX(c);
-  NO_NULL_PENDING(c, "cna_standardize");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
+  const bool from_nam = c->x_from_nam;
+  CNA_TRY(x_begin(c, "cna_standardize"));
   CNA_TRY(launch_standardize(c, center));
-  c->ncorrs_valid = false;
-  c->xq_valid = false; c->byp_valid = false; c->x_ident = false; c->gram_pre = false;
-  c->coef_early = false;
-  c->fdr_inline = false;
+  x_commit(c, from_nam, false, false, false);
   return 0;
 }
 
@@ -2049,13 +1984,9 @@ int cna_project(cna_ctx* c, const double* W, int n_w, double* out_local) {
   NO_NULL_PENDING(c, "cna_project");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (n_w < 1) CNA_FAIL(CNA_EINVAL, "n_w < 1");
-  const int Nx = c->Nx, ldx = c->ldx;
-  const int ldb = round_up(n_w, 16);
-  std::vector<double> B((size_t)ldx * ldb, 0.0);
-  for (int k = 0; k < Nx; ++k)
-    for (int j = 0; j < n_w; ++j) B[(size_t)k * ldb + j] = W[(size_t)k * n_w + j];
-  CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, (int64_t)sizeof(double) * ldx * ldb));
-  HIP_TRY(hipMemcpyAsync(c->scratch, B.data(), sizeof(double) * ldx * ldb, hipMemcpyHostToDevice, c->stream));
+  std::vector<double> B;
+  int ldb;
+  CNA_TRY(xb_operand(c, W, n_w, false, B, &ldb));
   CNA_TRY(dev_reserve(c, &c->scratch2, &c->scratch2_cap, (int64_t)sizeof(double) * std::max<int64_t>(c->nx, 1) * ldb));
   double* out = (double*)c->scratch2;
   CNA_TRY(launch_xb(c, (const double*)c->scratch, ldb, n_w, false, out, ldb));
@@ -2073,13 +2004,9 @@ int cna_project_keep(cna_ctx* c, const double* W, int n_w) {
   NO_NULL_PENDING(c, "cna_project_keep");
   if (!c->x_valid) CNA_FAIL(CNA_ESTATE, "X not available");
   if (n_w < 1) CNA_FAIL(CNA_EINVAL, "n_w < 1");
-  const int Nx = c->Nx, ldx = c->ldx;
-  const int ldb = round_up(n_w, 16);
-  std::vector<double> B((size_t)ldx * ldb, 0.0);
-  for (int k = 0; k < Nx; ++k)
-    for (int j = 0; j < n_w; ++j) B[(size_t)k * ldb + j] = W[(size_t)k * n_w + j];
-  CNA_TRY(dev_reserve(c, &c->scratch, &c->scratch_cap, (int64_t)sizeof(double) * ldx * ldb));
-  HIP_TRY(hipMemcpyAsync(c->scratch, B.data(), sizeof(double) * ldx * ldb, hipMemcpyHostToDevice, c->stream));
+  std::vector<double> B;
+  int ldb;
+  CNA_TRY(xb_operand(c, W, n_w, false, B, &ldb));
   CNA_TRY(dev_reserve(c, &c->proj, &c->proj_cap, (int64_t)sizeof(double) * std::max<int64_t>(c->nx, 1) * ldb));
   CNA_TRY(launch_xb(c, (const double*)c->scratch, ldb, n_w, false, (double*)c->proj, ldb));
   HIP_TRY(hipStreamSynchronize(c->stream));               // B is a local
@@ -2618,7 +2545,7 @@ static int ensure_cell_pinned(cna_ctx* c, int64_t n_out) {
     if (c->h_cell) HIP_TRY(hipHostFree(c->h_cell));
     c->h_cell = nullptr;
     c->coef_early = false;
-  c->fdr_inline = false;
+    c->fdr_inline = false;
     HIP_TRY(hipHostMalloc(&c->h_cell, (size_t)need, hipHostMallocDefault));
     c->h_cell_cap = need;
   }

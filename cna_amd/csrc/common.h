@@ -53,6 +53,9 @@ struct GramPlan {
   size_t smem = 0;
 };
 
+// Derived state: each flag below that says "still holds" is tagged with the transition of c_api.hip that clears it --
+// [void_x] X and what is derived from it, [void_walk] the walk and then X, [void_cells] the cell space and then the walk.
+// A new such flag goes into the transition of what it is derived from.
 struct cna_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -80,7 +83,7 @@ struct cna_ctx {
   int64_t null_stage_off = 0;          // h_res + off: the pinned copy of the prepared pass's exact cuts (its f64 rerun uploads them)
   std::atomic<int> null_pending{0};   // (read by the helper thread's cna_percell_fdr_copy_early, like the four flags below)
   int64_t gram_cap = 0;
-  int gram_n = 0;
+  int gram_n = 0;                      // [void_x] order of the Gram matrix in h_gram (0: none)
   std::atomic<int64_t> dev_bytes{0};   // (two host threads may reserve buffers of one context at once: the F-tests from the eigenvector thread)
   std::recursive_mutex alloc_mu;   // dev_alloc / dev_free / dev_reserve (two host threads may share the context)
 
@@ -125,7 +128,7 @@ struct cna_ctx {
   double* counts = nullptr;  // N
   void* cellinfo = nullptr;  // n_global x {1/colsums, sid}: one gather per edge in the first step
   int64_t cellinfo_cap = 0;
-  bool cellinfo_valid = false;
+  bool cellinfo_valid = false;   // [void_cells]
 
   // ---- diffusion state: scaled state T = s/colsums.  Rows: every global row (one rank; the all-gather exchange), or --
   // with the halo exchange (t_compact, round 5; SURVEY 8e: "GPU g owns rows ... of A and of S") -- this rank's n_local
@@ -146,20 +149,20 @@ struct cna_ctx {
   int64_t sp_pair_rows = 0;      // rows of sp_pair (pairs exist for this rank's own rows only when compact)
   double* T[2] = {nullptr, nullptr};
   int64_t t_cap = 0;  // doubles allocated per buffer
-  int t_cur = 0, t_width = 0, t_ld = 0, steps_done = 0;
-  bool t_valid = false;
+  int t_cur = 0, t_width = 0, t_ld = 0, steps_done = 0;   // steps_done: [void_walk]
+  bool t_valid = false;          // [void_walk]
   // opt-in (cna_set_state_f32): the scaled state BETWEEN two steps of a walk is stored in 4 bytes per entry
   // (sums still run in f64).  Halves what the dense step gathers; the NAM then equals the f64 one to ~1e-7 relative
   // instead of bit for bit.  t_f32[i]: what T[i] holds right now.
   bool state_f32_mode = false;
-  bool t_f32[2] = {false, false};
+  bool t_f32[2] = {false, false};   // [void_walk]
   double* dense_s = nullptr;  // unscaled local state of the dense diffusion (n_local x t_ld)
   int64_t dense_cap = 0;
 
   // ---- NAM (n_local x ld)
   double* nam = nullptr;
   int64_t nam_cap = 0;
-  bool nam_valid = false;
+  bool nam_valid = false;        // [void_walk]
 
   // ---- X (nx x ldx): selected NAM -> residualised NAM
   double* X = nullptr;
@@ -175,8 +178,8 @@ struct cna_ctx {
   int64_t* keep_idx = nullptr;    // active map: local NAM row of each X row; null = identity
   int64_t* keep_store = nullptr;  // allocation behind keep_idx
   int64_t keep_cap = 0;
-  bool x_valid = false, x_from_nam = false;
-  bool x_ident = false;            // X = standardised NAM, every cell, samples in place, nothing regressed out (cna_x_identity)
+  bool x_valid = false, x_from_nam = false;   // [void_x]
+  bool x_ident = false;            // [void_x] X = standardised NAM, every cell, samples in place, nothing regressed out (cna_x_identity)
   // The selection pass as a by-product of the walk's last step (cna_nam_select_hint): when the caller says which
   // standardised phenotype the analysis will use and nothing will be filtered or regressed out, the last step's
   // write-out also leaves X = centred / standardised NAM, its digit planes, the coefficients X.y/N and the
@@ -184,10 +187,10 @@ struct cna_ctx {
   // it has just written -- and that call then finds its work done (the 1.5 ms pass at 2M x 200 leaves the path).
   std::vector<double> byp_hint;    // y of a pending hint (consumed by the next last step)
   std::vector<double> byp_y;       // y the by-product on the device was made for
-  bool byp_valid = false;          // X / planes / coefficients on the device are that by-product
+  bool byp_valid = false;          // [void_x] X / planes / coefficients on the device are that by-product
   bool byp_with_q = false;
   bool byp_skip_nam = false;       // ... and it does not write the NAM (nam_lazy afterwards)
-  bool nam_lazy = false;           // the NAM is one more run of the last step away (c_api.hip:need_nam)
+  bool nam_lazy = false;           // [void_walk] the NAM is one more run of the last step away (c_api.hip:need_nam)
   int lazy_steps_before = 0;       // steps_done when that step was launched
   bool byp_arm = false;            // the launch being issued is that last step (launch_nam_step reads it)
   void* pair_buf = nullptr;        // {count, max bits} of every rank: the selection pass's two counters in one collective
@@ -204,7 +207,7 @@ struct cna_ctx {
   int auto_max = 0, auto_queued = 0;
   double* ncorrs = nullptr;
   int64_t ncorrs_cap = 0;
-  bool ncorrs_valid = false;
+  bool ncorrs_valid = false;   // [void_x]
 
   // ---- resident conditioned phenotypes Zc (ldx x zc_ld), zc_cols valid columns
   double* zc = nullptr;
@@ -219,7 +222,7 @@ struct cna_ctx {
   void* proj = nullptr;           // result of cna_project_keep (rows of X x proj_cols, leading dimension proj_ld)
   int64_t proj_cap = 0, proj_rows = 0;
   int proj_ld = 0, proj_cols = 0;
-  bool proj_valid = false;
+  bool proj_valid = false;        // [void_x]
   int null_prepared = 0;          // cna_null_local_prepare done, launch still to come
   double null_cut0 = 0, null_inv_step = 0, null_eps = 0;
   int null_has_obs = 0;
@@ -233,8 +236,8 @@ struct cna_ctx {
   double* coef_dev = nullptr;     // early copy of the per-cell coefficients (cna_percell_coef_launch): 2 x n_pad
   int64_t coef_dev_cap = 0;
   hipEvent_t coef_ready = nullptr, coef_copied = nullptr;
-  std::atomic<bool> coef_early{false};        // h_cell[0, n_out) already holds the coefficients of the current ncorrs
-  std::atomic<bool> fdr_inline{false};        // ... and h_cell[n_out, 2 n_out) the per-cell FDRs of the last local-null pass
+  std::atomic<bool> coef_early{false};        // [void_x] h_cell[0, n_out) already holds the coefficients of the current ncorrs
+  std::atomic<bool> fdr_inline{false};        // [void_x] ... and h_cell[n_out, 2 n_out) the per-cell FDRs of the last local-null pass
   double null_thr0 = 0, null_thr_step = 0;   // linear guess over the thresholds of the prepared pass
   std::atomic<bool> fdr_early_copied{false};  // cna_percell_fdr_copy_early took the FDR column of the pending pass ...
   std::atomic<bool> fdr_early_served{false};  // ... and cna_percell_fdr_pinned then returned that same column
@@ -262,7 +265,7 @@ struct cna_ctx {
   int64_t xq_cap = 0;             //   the pass that produced X (k_select_std) or by k_quant_x
   void* xq_scale = nullptr;
   int64_t xq_scale_cap = 0;
-  bool xq_valid = false;          // they describe the current X
+  bool xq_valid = false;          // [void_x] they describe the current X
   int64_t xq_rows = 0;
   int xq_KS = 0;
   bool i8_last = false;           // the last local-null pass took the integer path
@@ -281,7 +284,7 @@ struct cna_ctx {
   hipStream_t gram_stream = nullptr;
   int gram_stream_state = 0;             // 0: not created yet, 1: ready, -1: unavailable
   hipEvent_t gram_pre_done = nullptr, range_done = nullptr;
-  bool gram_pre = false;
+  bool gram_pre = false;                 // [void_x]
   bool gram_pre_pending = false;         // kernels of a ranged product may still run on gram_stream (nobody has waited for gram_pre_done yet)
   void* gram_part = nullptr;
   int64_t gram_part_cap = 0;

@@ -5,7 +5,14 @@ queue overflow, forced here through CNA_I8_QCAP), the fetch reruns it on the f64
 phenotypes and the exact cuts the launch saw.  The contract (csrc/c_api.hip: NO_NULL_PENDING): an entry point that would
 rewrite X or carve the scratch those cuts live in refuses with CNA_ESTATE while a pass is pending, changes nothing, and
 the fetch returns the f64 kernel's integers.  Also here: the FDR column the helper thread copies while a given-up pass is
-collected, and the Gram matrix queued with a selection that turns out to have cells of zero variance."""
+collected, and the Gram matrix queued with a selection that turns out to have cells of zero variance.
+
+State derived from X, the walk or the cells holds only as long as what it was derived from (csrc/c_api.hip: void_x,
+void_walk, void_cells; every producer of X goes through x_begin / x_commit).  The kept projection (cna_project_keep) and
+the Gram matrix refuse to be fetched once X has been rewritten, the walk restarted or the graph replaced; the
+coefficients of an analysis do not outlive its walk.  A walk with a selection hint while a pass is pending leaves X to
+that pass: the hint does not arm, the step writes the NAM, and the next selection is the separate pass of a walk without
+the hint, bit for bit (the by-product agrees with that pass to rounding, not bit for bit)."""
 import threading
 
 import numpy as np
@@ -263,3 +270,181 @@ def test_gram_queued_with_zero_variance_cells_is_dropped(eng, n_samples):
     want = X.T @ X
     np.testing.assert_array_equal(G, G.T)
     np.testing.assert_allclose(G, want, rtol=1e-12, atol=1e-12 * np.abs(want).max())
+
+
+NS = 30
+
+
+@pytest.fixture(scope='module')
+def small():
+    """Two small datasets of NS samples (the second one: another graph) and a standardised phenotype."""
+    from cna_amd import synth
+    data, _ = synth.make_dataset(4000, NS, k=15, seed=7)
+    other, _ = synth.make_dataset(3000, NS, k=15, seed=8)
+    y = np.random.RandomState(7).randn(NS)
+    return data, other, (y - y.mean()) / y.std()
+
+
+def _x_standardized(eng, data):
+    """The shared engine with the 3-step NAM of `data` resident and X = its standardised selection; returns the codes."""
+    eng.null_local_discard()
+    codes = _walk(eng, data, NS)
+    assert eng.select_standardized(None, None) == 0
+    return codes
+
+
+def _rewrite(eng, what, small, codes):
+    """One call that replaces X (or the walk, or the graph X was derived from)."""
+    from cna_amd import _ffi
+    data, other, y = small
+    rs = np.random.RandomState(3)
+    nx, Nx = eng.matrix_shape(_ffi.MAT_X)
+    Cm = np.ones((Nx, 1)) / np.sqrt(Nx)
+    batches = np.arange(Nx, dtype=np.int32) % 3
+    if what == 'select':
+        eng.select(None, None)
+    elif what == 'select_checked':
+        assert eng.select_checked(None, None) == 0
+    elif what == 'select_standardized':
+        assert eng.select_standardized(None, None) == 0
+    elif what == 'select_resid_bk':
+        assert eng.select_resid_bk(Cm, Cm.T.copy(), y, batches, 3) is not None
+    elif what == 'upload_x':
+        eng.upload_x(rs.randn(nx, Nx))
+    elif what == 'resid_apply':
+        eng.resid_apply(np.eye(Nx) - Cm @ Cm.T, True)
+    elif what == 'resid_lowrank':
+        eng.resid_lowrank(Cm, Cm.T.copy(), center=True, standardize=True)
+    elif what == 'resid_lowrank_bk':
+        eng.resid_lowrank_bk(Cm, Cm.T.copy(), y, batches, 3)
+    elif what == 'standardize':
+        eng.standardize(center=True)
+    elif what == 'restart':
+        assert eng.lib.cna_restart_nam(eng.h) == 0
+    elif what == 'set_samples':
+        eng.set_samples(codes, NS, np.bincount(codes, minlength=NS).astype(float))
+    else:
+        assert what == 'graph'
+        eng.ensure_graph(other.obsp['connectivities'])
+
+
+@pytest.mark.parametrize('what', ['select', 'upload_x', 'resid_lowrank', 'standardize', 'restart', 'graph'])
+def test_kept_projection_is_void_after(eng, small, what):
+    """cna_project_keep, then a new X, walk or graph: cna_fetch_rows(CNA_MAT_PROJ) refuses (CNA_ESTATE) and leaves
+    `out` untouched instead of returning the rows of the old X."""
+    from cna_amd import _ffi
+    codes = _x_standardized(eng, small[0])
+    X = eng.fetch_matrix(_ffi.MAT_X)
+    W = np.random.RandomState(5).randn(NS, 3)
+    eng.project_keep(W)
+    np.testing.assert_allclose(eng.fetch_rows(_ffi.MAT_PROJ), X @ W, rtol=1e-12, atol=1e-12 * np.abs(X @ W).max())
+    _rewrite(eng, what, small, codes)
+    out = np.full((X.shape[0], 3), -1.0)
+    assert eng.lib.cna_fetch_rows(eng.h, _ffi.MAT_PROJ, None, 0, None, 0, out.ctypes.data, 0) == -4
+    assert (out == -1.0).all()
+
+
+@pytest.mark.parametrize('what', ['select', 'select_checked', 'select_standardized', 'select_resid_bk', 'upload_x',
+                                  'resid_apply', 'resid_lowrank', 'resid_lowrank_bk', 'standardize'])
+def test_gram_matrix_is_void_after_x_is_rewritten(eng, small, what):
+    """cna_gram_launch, then a rewrite of X: cna_gram_fetch refuses (CNA_ESTATE) instead of returning X^T X of the old
+    X; a fresh cna_gram_launch gives X^T X of the current X."""
+    from cna_amd import _ffi
+    codes = _x_standardized(eng, small[0])
+    assert eng.lib.cna_gram_launch(eng.h) == 0
+    G = np.full((NS, NS), -1.0)
+    assert eng.lib.cna_gram_fetch(eng.h, G.ctypes.data) == 0
+    _rewrite(eng, what, small, codes)
+    G = np.full((NS, NS), -1.0)
+    assert eng.lib.cna_gram_fetch(eng.h, G.ctypes.data) == -4
+    assert (G == -1.0).all()
+    assert eng.lib.cna_gram_launch(eng.h) == 0
+    assert eng.lib.cna_gram_fetch(eng.h, G.ctypes.data) == 0
+    X = eng.fetch_matrix(_ffi.MAT_X)
+    want = X.T @ X
+    np.testing.assert_array_equal(G, G.T)
+    np.testing.assert_allclose(G, want, rtol=1e-12, atol=1e-12 * np.abs(want).max())
+
+
+@pytest.mark.parametrize('what', ['restart', 'set_samples'])
+def test_coefficients_do_not_outlive_the_walk(eng, small, what):
+    """select_standardized with y, then a new walk begins: the coefficients of the old one are not served
+    (cna_percell_coef_launch raises CNA_ESTATE) and X is no longer the resident walk's (cna_x_identity = 0)."""
+    from cna_amd import _ffi
+    data, other, y = small
+    eng.null_local_discard()
+    codes = _walk(eng, data, NS)
+    nz, _ = eng.select_standardized(None, None, y=y)
+    assert nz == 0 and eng.x_identity_resident()
+    assert eng.percell_coef_launch()
+    eng.percell_coef_wait()
+    _rewrite(eng, what, small, codes)
+    with pytest.raises(_ffi.CnaHipError, match=r'status -4\)'):
+        eng.percell_coef_launch()
+    assert not eng.x_identity_resident()
+
+
+NW, PW = 96, 256          # more than 64 samples: the walk's last step can leave the selection by-product (t_ld > 64)
+
+
+@pytest.fixture(scope='module')
+def wide(eng):
+    """10 000 cells x NW samples: X = the standardised 3-step NAM with y, Zc conditioned; what a pass on it must return
+    (the f64 kernel's tail sums and the observed counts), and X4 = the separate selection pass over a 4-step walk."""
+    from cna_amd import _ffi, synth
+    data, _ = synth.make_dataset(10000, NW, k=15, seed=31)
+    rs = np.random.RandomState(6)
+    y = rs.randn(NW)
+    y = (y - y.mean()) / y.std()
+    Y = np.column_stack([y, rs.randn(NW, PW)])
+    eng.null_local_discard()
+    codes = _walk(eng, data, NW)
+    eng.set_samples(codes, NW, np.bincount(codes, minlength=NW).astype(float))
+    eng.nam_steps(4)
+    assert eng.select_standardized(None, None, y=y)[0] == 0
+    X4 = eng.fetch_matrix(_ffi.MAT_X)
+    thr = edges = None
+
+    def setup(eng):
+        nonlocal thr, edges
+        eng.null_local_discard()
+        codes = _walk(eng, data, NW)
+        nz, maxabs = eng.select_standardized(None, None, y=y)
+        assert nz == 0
+        if thr is None:
+            maxcorr = max(maxabs, 0.001)
+            thr = np.arange(maxcorr / 4, maxcorr, maxcorr / 400)
+            z2 = thr ** 2
+            edges = z2 - 1e-8 - 1e-5 * z2
+        eng.condition(np.eye(NW), Y)
+        return codes, thr, edges
+    codes, thr, edges = setup(eng)
+    sums = eng.null_local_resident(1, PW, edges).sum(axis=0)       # want_tails: the f64 kernel
+    ranks, numdet = eng.obs_counts(edges, thr)
+    return dict(setup=setup, y=y, X4=X4, sums=sums, ranks=ranks, numdet=numdet)
+
+
+@pytest.mark.parametrize('give_up', [False, True])
+def test_walk_with_a_selection_hint_while_a_pass_is_pending(eng, wide, monkeypatch, give_up):
+    """A pass is pending (its integer kernel kept or given up) when a walk of another length with a selection hint runs:
+    the hint does not arm, so the fetch -- a given-up pass reruns in f64 on X -- returns the f64 kernel's sums of the
+    launch's X; the next selection is then the separate pass, as after the same walk without a hint."""
+    from cna_amd import _ffi
+    codes, thr, edges = wide['setup'](eng)
+    if give_up:
+        monkeypatch.setenv('CNA_I8_QCAP', '8')
+    else:
+        monkeypatch.delenv('CNA_I8_QCAP', raising=False)
+    eng.null_local_launch(1, PW, edges, thr)
+    eng.set_samples(codes, NW, np.bincount(codes, minlength=NW).astype(float))
+    eng.nam_select_hint(wide['y'])
+    eng.nam_steps(4)
+    sums, ranks, numdet = eng.null_local_fetch()
+    monkeypatch.delenv('CNA_I8_QCAP', raising=False)
+    used, rechecked, fallback = eng.null_local_i8_stats()
+    assert used and fallback == give_up
+    np.testing.assert_array_equal(sums, wide['sums'])
+    np.testing.assert_array_equal(ranks, wide['ranks'])
+    np.testing.assert_array_equal(numdet, wide['numdet'])
+    assert eng.select_standardized(None, None, y=wide['y'])[0] == 0
+    np.testing.assert_array_equal(eng.fetch_matrix(_ffi.MAT_X), wide['X4'])
