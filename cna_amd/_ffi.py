@@ -133,6 +133,12 @@ SIGNATURES = {
     'cna_prof_reset': (C.c_int, [c_ctx]),
     'cna_prof_get': (C.c_int, [c_ctx, C.c_int, c_f64p, c_i64p]),
     'cna_kernel_name': (C.c_char_p, [C.c_int]),
+    'cna_expr_upload_dense': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    'cna_expr_upload_sparse': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                         C.c_int, C.c_int, C.c_int]),
+    'cna_expr_drop': (C.c_int, [c_ctx]),
+    'cna_expr_shape': (C.c_int, [c_ctx, c_i64p, c_i64p, c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_i64p]),
+    'cna_gene_corr': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 MAT_NAM, MAT_X, MAT_PROJ = 0, 1, 2

@@ -293,6 +293,10 @@ struct cna_ctx {
   void* gram_tiles_ptr = nullptr;
   int64_t gram_tiles_cap = 0;
 
+  // ---- resident expression matrix and the work buffers of cna_gene_corr (genes.hip owns all of it: caller's cell order,
+  // a stream of its own; derived from nothing above, so none of the transitions of c_api.hip concerns it)
+  void* expr = nullptr;
+
   // ---- profiling
   bool prof = false;
   uint64_t prof_mask = ~0ull;      // kernel ids that are timed while prof is on (cna_prof_enable level 2: the walk and the communication spans)
@@ -320,6 +324,9 @@ int dev_alloc(cna_ctx* c, void** p, size_t bytes);
 int dev_free(cna_ctx* c, void* p, size_t bytes);
 // grow-only buffer: (re)allocates *p when cap < need (contents discarded)
 int dev_reserve(cna_ctx* c, void** p, int64_t* cap_bytes, int64_t need_bytes);
+
+// genes.hip: frees the resident expression matrix and its state (cna_ctx_destroy)
+void expr_destroy(cna_ctx* c);
 
 // ---- collectives (comm.hip)
 inline bool comm_active(const cna_ctx* c) { return c->comm != nullptr || c->shm != nullptr; }

@@ -1,0 +1,819 @@
+// Per-gene Pearson correlation to per-cell columns (the neighbourhood coefficient of cna.tl.association, NAM PC
+// loadings, ...) over an expression matrix that stays resident on the device.  Replaces the host line of the
+// reference's workflow (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient"):
+//     d.var['corr_case'] = np.corrcoef(d.obs.male_coef.values.reshape(1,-1), d.X, rowvar=False)[0,1:]
+//
+// Nothing here reads or writes the state of c_api.hip (graph, walk, NAM, X, cell order): the matrix and the key columns
+// are in the CALLER's cell order, the buffers and the stream are this file's own (cna_ctx::expr).
+//
+//   k_key_stats     per key column: finite count, mean, sum (v - mean), sum (v - mean)^2, min, max (fixed-order sums)
+//   k_key_table     cells x Q table of centred key values (0 where the cell is left out) + one mask word per cell
+//   k_gc_dense      X is cells x genes: lane = gene, a wave walks down a slab of cells (coalesced rows, the key values
+//                   of a cell are wave-uniform); partial sums per slab with plain stores
+//   k_gc_sparse     gene-major lists {cell, value}: one wave per chunk of a gene's list, gathers the cell's table row;
+//                   partial sums per chunk with plain stores
+//   k_gc_finish_*   adds the partials of a gene in slab / chunk order and turns them into r
+//   k_tr_*          counting transpose of a CSR upload into the gene-major form, stable in the cell index
+//
+// Result sums take a fixed order (no floating-point atomics): two runs on one input give the same bits.  Integer
+// atomics only count and hand out cursors.
+#include "common.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+namespace {
+
+constexpr int GC_MAXQ = 16;
+constexpr int KS_LD = 8;   // doubles per key in the key statistics block: n, mean, sum vc^2, sum vc, min, max
+
+struct Buf {
+  void* p = nullptr;
+  int64_t cap = 0;
+};
+
+struct ExprState {
+  hipStream_t st = nullptr;
+  int format = 0;   // 0: none, 1: dense cells x genes, 2: gene-major lists
+  int is_f64 = 0;
+  int64_t n = 0, G = 0, nnz = 0;
+  int64_t n_uploads = 0;
+  Buf X;                           // dense
+  Buf gptr, gcell, gval;           // gene-major: G + 1 offsets, cell of every entry (ascending inside a gene), values
+  Buf chunk_lo, chunk_gene, gchunk;   // first entry / gene of every chunk; first chunk of every gene (G + 1)
+  int64_t nchunks = 0, chunk_len = 0;
+  // per call (grow-only until the matrix is dropped)
+  Buf vraw, vtab, vmask, kstat, part, rout, flag;
+};
+
+inline ExprState* state_of(cna_ctx* c) { return static_cast<ExprState*>(c->expr); }
+
+int buf_free(cna_ctx* c, Buf& b) {
+  if (b.p) dev_free(c, b.p, (size_t)b.cap);
+  b.p = nullptr;
+  b.cap = 0;
+  return 0;
+}
+
+int buf_need(cna_ctx* c, ExprState* s, Buf& b, int64_t bytes) {
+  if (b.p && b.cap >= bytes) return 0;
+  if (b.p) {
+    HIP_TRY(hipStreamSynchronize(s->st));
+    buf_free(c, b);
+  }
+  if (bytes < 256) bytes = 256;
+  CNA_TRY(dev_alloc(c, &b.p, (size_t)bytes));
+  b.cap = bytes;
+  return 0;
+}
+
+void release_matrix(cna_ctx* c, ExprState* s) {
+  (void)hipStreamSynchronize(s->st);
+  for (Buf* b : {&s->X, &s->gptr, &s->gcell, &s->gval, &s->chunk_lo, &s->chunk_gene, &s->gchunk, &s->vraw, &s->vtab,
+                 &s->vmask, &s->kstat, &s->part, &s->rout, &s->flag})
+    buf_free(c, *b);
+  s->format = 0;
+  s->n = s->G = s->nnz = 0;
+  s->nchunks = s->chunk_len = 0;
+}
+
+int get_state(cna_ctx* c, ExprState** out) {
+  if (!c->expr) {
+    ExprState* s = new ExprState();
+    hipError_t e = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      delete s;
+      cna_set_error(std::string("hipStreamCreate: ") + hipGetErrorString(e));
+      return (int)e;
+    }
+    c->expr = s;
+  }
+  *out = state_of(c);
+  return 0;
+}
+
+// ------------------------------------------------------------------ key columns
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.79769313486231570815e308; }
+
+// one block of 1024 threads per key: thread t adds the cells t, t + 1024, ...; the 1024 partial sums are folded by a
+// fixed tree -- the same bits on every run
+__global__ __launch_bounds__(1024) void k_key_stats(const double* __restrict__ V, int64_t n, double* __restrict__ ks) {
+  __shared__ double sh[4][1024];
+  const int j = blockIdx.x, t = threadIdx.x;
+  const double* v = V + (int64_t)j * n;
+  double cnt = 0, sum = 0, mn = INFINITY, mx = -INFINITY;
+  for (int64_t i = t; i < n; i += 1024) {
+    const double x = v[i];
+    if (finite_d(x)) {
+      cnt += 1.0;
+      sum += x;
+      mn = fmin(mn, x);
+      mx = fmax(mx, x);
+    }
+  }
+  sh[0][t] = cnt; sh[1][t] = sum; sh[2][t] = mn; sh[3][t] = mx;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if (t < w) {
+      sh[0][t] += sh[0][t + w];
+      sh[1][t] += sh[1][t + w];
+      sh[2][t] = fmin(sh[2][t], sh[2][t + w]);
+      sh[3][t] = fmax(sh[3][t], sh[3][t + w]);
+    }
+    __syncthreads();
+  }
+  const double N = sh[0][0], mean = N > 0 ? sh[1][0] / N : 0.0, vmin = sh[2][0], vmax = sh[3][0];
+  __syncthreads();
+  double s1 = 0, s2 = 0;
+  for (int64_t i = t; i < n; i += 1024) {
+    const double x = v[i];
+    if (finite_d(x)) {
+      const double d = x - mean;
+      s1 += d;
+      s2 += d * d;
+    }
+  }
+  sh[0][t] = s1; sh[1][t] = s2;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if (t < w) {
+      sh[0][t] += sh[0][t + w];
+      sh[1][t] += sh[1][t + w];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    double* o = ks + j * KS_LD;
+    o[0] = N; o[1] = mean; o[2] = sh[1][0]; o[3] = sh[0][0]; o[4] = vmin; o[5] = vmax; o[6] = 0; o[7] = 0;
+  }
+}
+
+// cell-major table: one gather brings all Q centred values of a cell.  flag |= 1 when the keys' masks differ in a cell.
+__global__ __launch_bounds__(256) void k_key_table(const double* __restrict__ V, int64_t n, int q, int Q,
+                                                   const double* __restrict__ ks, double* __restrict__ tab,
+                                                   uint32_t* __restrict__ mask, int* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t m = 0;
+  for (int j = 0; j < Q; ++j) {
+    double vc = 0.0;
+    if (j < q) {
+      const double x = V[(int64_t)j * n + i];
+      if (finite_d(x)) {
+        vc = x - ks[j * KS_LD + 1];
+        m |= 1u << j;
+      }
+    }
+    tab[i * Q + j] = vc;
+  }
+  mask[i] = m;
+  if (m != 0 && m != (q >= 32 ? ~0u : (1u << q) - 1u)) atomicOr(flag, 1);
+}
+
+// ------------------------------------------------------------------ dense
+// Field order of a partial record (F = 4 S + Q doubles, S = 1 when the keys share one mask, else Q):
+//   [s]: sum x   [S + s]: sum x^2   [2S + s]: min x   [3S + s]: max x   [4S + j]: sum x (v_j - mean_j)
+template <typename T, int Q, bool SHARED>
+__global__ __launch_bounds__(64) void k_gc_dense(const T* __restrict__ X, int64_t n, int64_t G, int64_t slab_rows,
+                                                 const double* __restrict__ tab, const uint32_t* __restrict__ mask,
+                                                 double* __restrict__ part) {
+  constexpr int S = SHARED ? 1 : Q;
+  constexpr int F = 4 * S + Q;
+  constexpr int U = 8;
+  const int64_t g = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  const bool act = g < G;
+  const int64_t gl = act ? g : G - 1;          // idle lanes of the last gene block reload its last gene; nothing is stored
+  const int64_t r0 = (int64_t)blockIdx.y * slab_rows;
+  const int64_t r1 = r0 + slab_rows < n ? r0 + slab_rows : n;
+  double sx[S], sxx[S], sxv[Q];
+  T mn[S], mx[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    sx[s] = 0; sxx[s] = 0;
+    mn[s] = (T)INFINITY; mx[s] = (T)-INFINITY;
+  }
+#pragma unroll
+  for (int j = 0; j < Q; ++j) sxv[j] = 0;
+  for (int64_t r = r0; r < r1; r += U) {
+    T xs[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t rr = r + u < r1 ? r + u : r1 - 1;
+      xs[u] = X[rr * G + gl];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (r + u >= r1) break;
+      const uint32_t m = mask[r + u];          // wave-uniform: a scalar load and a scalar branch
+      if (m == 0) continue;
+      const double* v = tab + (r + u) * Q;
+      const double x = (double)xs[u];
+      if (SHARED) {
+        sx[0] += x;
+        sxx[0] = fma(x, x, sxx[0]);
+        mn[0] = xs[u] < mn[0] ? xs[u] : mn[0];
+        mx[0] = xs[u] > mx[0] ? xs[u] : mx[0];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) sxv[j] = fma(x, v[j], sxv[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+          if (m >> j & 1) {
+            sx[j] += x;
+            sxx[j] = fma(x, x, sxx[j]);
+            mn[j] = xs[u] < mn[j] ? xs[u] : mn[j];
+            mx[j] = xs[u] > mx[j] ? xs[u] : mx[j];
+            sxv[j] = fma(x, v[j], sxv[j]);
+          }
+        }
+      }
+    }
+  }
+  if (!act) return;
+  double* o = part + (int64_t)blockIdx.y * F * G + g;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    o[(int64_t)(s)*G] = sx[s];
+    o[(int64_t)(S + s) * G] = sxx[s];
+    o[(int64_t)(2 * S + s) * G] = (double)mn[s];
+    o[(int64_t)(3 * S + s) * G] = (double)mx[s];
+  }
+#pragma unroll
+  for (int j = 0; j < Q; ++j) o[(int64_t)(4 * S + j) * G] = sxv[j];
+}
+
+// r of one (gene, key) from its sums.  cnt: entries that were added (dense: every kept cell; gene-major lists: the
+// stored ones -- the others are zeros).  Constant genes and keys are decided exactly: minimum == maximum.
+__device__ __forceinline__ double gc_r(double sx, double sxx, double mn, double mx, double cnt, double sxv,
+                                       const double* __restrict__ ks) {
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double N = ks[0];
+  if (N < 2.0) return nan;
+  if (cnt < N) {
+    mn = fmin(mn, 0.0);
+    mx = fmax(mx, 0.0);
+  }
+  if (!(ks[4] < ks[5]) || mn == mx) return nan;
+  const double mean = sx / N;
+  const double varx = sxx - sx * mean;
+  const double cov = sxv - mean * ks[3];
+  double r = cov / sqrt(varx) / sqrt(ks[2]);
+  if (r > 1.0) r = 1.0;
+  if (r < -1.0) r = -1.0;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void k_gc_finish_dense(const double* __restrict__ part, int64_t G, int nslab, int q, int Q,
+                                                         int S, const double* __restrict__ ks, double* __restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G) return;
+  const int F = 4 * S + Q;
+  double sx = 0, sxx = 0, mn = INFINITY, mx = -INFINITY;
+  for (int j = 0; j < q; ++j) {
+    const int s = S == 1 ? 0 : j;
+    if (j == 0 || S != 1) {
+      sx = 0; sxx = 0; mn = INFINITY; mx = -INFINITY;
+      for (int p = 0; p < nslab; ++p) {
+        const double* o = part + (int64_t)p * F * G + g;
+        sx += o[(int64_t)s * G];
+        sxx += o[(int64_t)(S + s) * G];
+        mn = fmin(mn, o[(int64_t)(2 * S + s) * G]);
+        mx = fmax(mx, o[(int64_t)(3 * S + s) * G]);
+      }
+    }
+    double sxv = 0;
+    for (int p = 0; p < nslab; ++p) sxv += part[((int64_t)p * F + 4 * S + j) * G + g];
+    out[(int64_t)j * G + g] = gc_r(sx, sxx, mn, mx, ks[j * KS_LD], sxv, ks + j * KS_LD);
+  }
+}
+
+// ------------------------------------------------------------------ gene-major lists
+__device__ __forceinline__ double wave_min_any(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max_any(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Field order of a chunk's record (F = 5 S + Q doubles): as in the dense kernel, then [4S + s]: entries added,
+// [5S + j]: sum x (v_j - mean_j)
+template <typename T, int Q, bool SHARED>
+__global__ __launch_bounds__(256) void k_gc_sparse(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
+                                                   const int64_t* __restrict__ gptr, int64_t nchunks, int64_t chunk_len,
+                                                   const int32_t* __restrict__ gcell, const T* __restrict__ gval,
+                                                   const double* __restrict__ tab, const uint32_t* __restrict__ mask,
+                                                   double* __restrict__ part) {
+  constexpr int S = SHARED ? 1 : Q;
+  constexpr int F = 5 * S + Q;
+  const int64_t ch = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (ch >= nchunks) return;
+  const int64_t lo = chunk_lo[ch];
+  const int64_t end = gptr[chunk_gene[ch] + 1];
+  const int64_t hi = lo + chunk_len < end ? lo + chunk_len : end;
+  double sx[S], sxx[S], mn[S], mx[S], cnt[S], sxv[Q];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    sx[s] = 0; sxx[s] = 0; cnt[s] = 0;
+    mn[s] = INFINITY; mx[s] = -INFINITY;
+  }
+#pragma unroll
+  for (int j = 0; j < Q; ++j) sxv[j] = 0;
+#pragma unroll 2
+  for (int64_t e = lo + lane; e < hi; e += 64) {
+    const int64_t cell = gcell[e];
+    const double x = (double)gval[e];
+    const uint32_t m = mask[cell];
+    if (m == 0) continue;
+    double v[Q];
+    const double* row = tab + cell * Q;
+#pragma unroll
+    for (int j = 0; j < Q; ++j) v[j] = row[j];
+    if (SHARED) {
+      sx[0] += x;
+      sxx[0] = fma(x, x, sxx[0]);
+      mn[0] = fmin(mn[0], x);
+      mx[0] = fmax(mx[0], x);
+      cnt[0] += 1.0;
+#pragma unroll
+      for (int j = 0; j < Q; ++j) sxv[j] = fma(x, v[j], sxv[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < Q; ++j) {
+        if (m >> j & 1) {
+          sx[j] += x;
+          sxx[j] = fma(x, x, sxx[j]);
+          mn[j] = fmin(mn[j], x);
+          mx[j] = fmax(mx[j], x);
+          cnt[j] += 1.0;
+          sxv[j] = fma(x, v[j], sxv[j]);
+        }
+      }
+    }
+  }
+  double* o = part + ch * F;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const double a = wave_sum(sx[s]), b = wave_sum(sxx[s]), c0 = wave_min_any(mn[s]), c1 = wave_max_any(mx[s]),
+                 d = wave_sum(cnt[s]);
+    if (lane == 0) {
+      o[s] = a; o[S + s] = b; o[2 * S + s] = c0; o[3 * S + s] = c1; o[4 * S + s] = d;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < Q; ++j) {
+    const double a = wave_sum(sxv[j]);
+    if (lane == 0) o[5 * S + j] = a;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gc_finish_sparse(const double* __restrict__ part, const int64_t* __restrict__ gchunk,
+                                                          int64_t G, int q, int Q, int S, const double* __restrict__ ks,
+                                                          double* __restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G) return;
+  const int F = 5 * S + Q;
+  const int64_t c0 = gchunk[g], c1 = gchunk[g + 1];
+  double sx = 0, sxx = 0, mn = INFINITY, mx = -INFINITY, cnt = 0;
+  for (int j = 0; j < q; ++j) {
+    const int s = S == 1 ? 0 : j;
+    if (j == 0 || S != 1) {
+      sx = 0; sxx = 0; mn = INFINITY; mx = -INFINITY; cnt = 0;
+      for (int64_t ch = c0; ch < c1; ++ch) {     // chunk order: the order of the cells
+        const double* o = part + ch * F;
+        sx += o[s];
+        sxx += o[S + s];
+        mn = fmin(mn, o[2 * S + s]);
+        mx = fmax(mx, o[3 * S + s]);
+        cnt += o[4 * S + s];
+      }
+    }
+    double sxv = 0;
+    for (int64_t ch = c0; ch < c1; ++ch) sxv += part[ch * F + 5 * S + j];
+    out[(int64_t)j * G + g] = gc_r(sx, sxx, mn, mx, cnt, sxv, ks + j * KS_LD);
+  }
+}
+
+// ------------------------------------------------------------------ upload helpers
+// indices as the caller stores them (4 or 8 bytes) -> int32, checked against [0, limit); offsets -> int64
+// (src may be dst when the indices already take 4 bytes: the pass then only checks)
+__global__ __launch_bounds__(256) void k_narrow_idx(const void* src, int index_bytes, int64_t count, int64_t limit, int32_t* dst,
+                                                    int* __restrict__ bad) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const int64_t v = index_bytes == 8 ? static_cast<const int64_t*>(src)[i] : (int64_t) static_cast<const int32_t*>(src)[i];
+    if (v < 0 || v >= limit) {
+      atomicOr(bad, 1);
+      dst[i] = 0;
+    } else {
+      dst[i] = (int32_t)v;
+    }
+  }
+}
+
+// CSR -> gene-major, stable in the cell index.  The cells are cut into B blocks of rows_per_block rows:
+//   k_tr_count  cnt[b][g] = entries of gene g in block b (integer atomics)
+//   k_tr_scan   per gene: cnt[b][g] -> entries of g in the blocks before b; total[g]
+//   k_tr_fill   one workgroup per block walks its rows IN ORDER (a barrier between two rows): an entry of gene g goes to
+//               gptr[g] + cursor[b][g]++.  A row names a gene once (canonical input), so within a gene the cells ascend.
+__global__ __launch_bounds__(256) void k_tr_count(const int64_t* __restrict__ rptr, const int32_t* __restrict__ ridx, int64_t n,
+                                                  int64_t G, int64_t rows_per_block, unsigned int* __restrict__ cnt) {
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+  if (r0 >= r1) return;
+  unsigned int* mine = cnt + (int64_t)blockIdx.x * G;
+  for (int64_t e = rptr[r0] + threadIdx.x; e < rptr[r1]; e += blockDim.x) atomicAdd(mine + ridx[e], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_tr_scan(unsigned int* __restrict__ cnt, int64_t G, int B, int64_t* __restrict__ total) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G) return;
+  int64_t run = 0;
+  for (int b = 0; b < B; ++b) {
+    const unsigned int t = cnt[(int64_t)b * G + g];
+    cnt[(int64_t)b * G + g] = (unsigned int)run;
+    run += t;
+  }
+  total[g] = run;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_tr_fill(const int64_t* __restrict__ rptr, const int32_t* __restrict__ ridx,
+                                                 const T* __restrict__ rval, int64_t n, int64_t G, int64_t rows_per_block,
+                                                 unsigned int* __restrict__ cnt, const int64_t* __restrict__ gptr,
+                                                 int32_t* __restrict__ gcell, T* __restrict__ gval) {
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+  unsigned int* mine = cnt + (int64_t)blockIdx.x * G;
+  for (int64_t r = r0; r < r1; ++r) {
+    const int64_t lo = rptr[r], hi = rptr[r + 1];
+    for (int64_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
+      const int32_t g = ridx[e];
+      const int64_t pos = gptr[g] + (int64_t)atomicAdd(mine + g, 1u);
+      gcell[pos] = (int32_t)r;
+      gval[pos] = rval[e];
+    }
+    __syncthreads();
+  }
+}
+
+// offsets the caller stores in 4 or 8 bytes -> int64 on the host, checked: start at 0, never fall, end at nnz
+bool widen_offsets(const void* p, int index_bytes, int64_t count, int64_t nnz, std::vector<int64_t>& out) {
+  out.resize((size_t)count);
+  for (int64_t i = 0; i < count; ++i)
+    out[(size_t)i] = index_bytes == 8 ? static_cast<const int64_t*>(p)[i] : (int64_t) static_cast<const int32_t*>(p)[i];
+  if (out[0] != 0 || out[(size_t)count - 1] != nnz) return false;
+  for (int64_t i = 1; i < count; ++i)
+    if (out[(size_t)i] < out[(size_t)i - 1]) return false;
+  return true;
+}
+
+// chunks of the gene lists (Appendix B's split rule: a list longer than a chunk is cut into fixed chunks summed by
+// separate waves, the partials are added in chunk order)
+int build_chunks(cna_ctx* c, ExprState* s, const std::vector<int64_t>& gptr) {
+  const int64_t waves = 256 * 16;
+  int64_t len = s->nnz / (waves * 4);
+  len = std::max<int64_t>(1024, std::min<int64_t>(65536, len));
+  len = (len + 63) / 64 * 64;
+  std::vector<int64_t> lo, first((size_t)s->G + 1);
+  std::vector<int32_t> gene;
+  for (int64_t g = 0; g < s->G; ++g) {
+    first[(size_t)g] = (int64_t)lo.size();
+    for (int64_t e = gptr[(size_t)g]; e < gptr[(size_t)g + 1]; e += len) {
+      lo.push_back(e);
+      gene.push_back((int32_t)g);
+    }
+  }
+  first[(size_t)s->G] = (int64_t)lo.size();
+  s->nchunks = (int64_t)lo.size();
+  s->chunk_len = len;
+  CNA_TRY(buf_need(c, s, s->chunk_lo, 8 * std::max<int64_t>(1, s->nchunks)));
+  CNA_TRY(buf_need(c, s, s->chunk_gene, 4 * std::max<int64_t>(1, s->nchunks)));
+  CNA_TRY(buf_need(c, s, s->gchunk, 8 * (s->G + 1)));
+  if (s->nchunks) {
+    HIP_TRY(hipMemcpyAsync(s->chunk_lo.p, lo.data(), 8 * (size_t)s->nchunks, hipMemcpyHostToDevice, s->st));
+    HIP_TRY(hipMemcpyAsync(s->chunk_gene.p, gene.data(), 4 * (size_t)s->nchunks, hipMemcpyHostToDevice, s->st));
+  }
+  HIP_TRY(hipMemcpyAsync(s->gchunk.p, first.data(), 8 * (size_t)(s->G + 1), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return 0;
+}
+
+int upload_sparse(cna_ctx* c, ExprState* s, const void* indptr, const void* indices, const void* data, int64_t n, int64_t G,
+                  int64_t nnz, int index_bytes, int is_f64, int is_csc) {
+  const int64_t vb = is_f64 ? 8 : 4;
+  const int64_t nmajor = is_csc ? G : n;
+  std::vector<int64_t> off;
+  if (!widen_offsets(indptr, index_bytes, nmajor + 1, nnz, off))
+    CNA_FAIL(CNA_EINVAL, "expression matrix: indptr must start at 0, never fall and end at nnz");
+  s->n = n; s->G = G; s->nnz = nnz; s->is_f64 = is_f64;
+  Buf raw_idx, raw_val, rptr, ridx, cnt, total, bad;
+  int rc = 0;
+  auto cleanup = [&]() {
+    (void)hipStreamSynchronize(s->st);
+    for (Buf* b : {&raw_idx, &raw_val, &rptr, &ridx, &cnt, &total, &bad}) buf_free(c, *b);
+  };
+#define UP_TRY(expr)                 \
+  do {                               \
+    rc = (expr);                     \
+    if (rc != 0) {                   \
+      cleanup();                     \
+      return rc;                     \
+    }                                \
+  } while (0)
+#define UP_HIP(expr)                                                                  \
+  do {                                                                                \
+    hipError_t _e = (expr);                                                           \
+    if (_e != hipSuccess) {                                                           \
+      cna_set_error(std::string(#expr) + ": " + hipGetErrorString(_e));               \
+      cleanup();                                                                      \
+      return (int)_e;                                                                 \
+    }                                                                                 \
+  } while (0)
+  const int64_t nz1 = std::max<int64_t>(1, nnz);
+  const unsigned grid_e = (unsigned)std::min<int64_t>((nz1 + 255) / 256, 1 << 20);
+  UP_TRY(buf_need(c, s, bad, 256));
+  UP_HIP(hipMemsetAsync(bad.p, 0, 4, s->st));
+  UP_TRY(buf_need(c, s, s->gptr, 8 * (G + 1)));
+  UP_TRY(buf_need(c, s, s->gcell, 4 * nz1));
+  UP_TRY(buf_need(c, s, s->gval, vb * nz1));
+  std::vector<int64_t> gptr_h;
+  int bad_h = 0;
+  if (is_csc) {
+    // gene-major already: the cell of every entry, narrowed to 4 bytes and checked on the device
+    if (index_bytes == 8) {
+      UP_TRY(buf_need(c, s, raw_idx, 8 * nz1));
+      UP_HIP(hipMemcpyAsync(raw_idx.p, indices, 8 * (size_t)nnz, hipMemcpyHostToDevice, s->st));
+      hipLaunchKernelGGL(k_narrow_idx, dim3(grid_e), dim3(256), 0, s->st, raw_idx.p, 8, nnz, n, (int32_t*)s->gcell.p, (int*)bad.p);
+    } else {
+      UP_HIP(hipMemcpyAsync(s->gcell.p, indices, 4 * (size_t)nnz, hipMemcpyHostToDevice, s->st));
+      hipLaunchKernelGGL(k_narrow_idx, dim3(grid_e), dim3(256), 0, s->st, s->gcell.p, 4, nnz, n, (int32_t*)s->gcell.p, (int*)bad.p);
+    }
+    UP_HIP(hipGetLastError());
+    UP_HIP(hipMemcpyAsync(s->gval.p, data, (size_t)(vb * nnz), hipMemcpyHostToDevice, s->st));
+    UP_HIP(hipMemcpyAsync(&bad_h, bad.p, 4, hipMemcpyDeviceToHost, s->st));
+    UP_HIP(hipStreamSynchronize(s->st));
+    if (bad_h) {
+      cleanup();
+      CNA_FAIL(CNA_EINVAL, "expression matrix: a row index lies outside [0, n_cells)");
+    }
+    gptr_h = off;
+  } else {
+    // the transpose needs the rows' indices and values beside the gene-major copy for a moment
+    UP_TRY(buf_need(c, s, rptr, 8 * (n + 1)));
+    UP_TRY(buf_need(c, s, ridx, 4 * nz1));
+    UP_TRY(buf_need(c, s, raw_val, vb * nz1));
+    UP_HIP(hipMemcpyAsync(rptr.p, off.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s->st));
+    if (index_bytes == 8) {
+      UP_TRY(buf_need(c, s, raw_idx, 8 * nz1));
+      UP_HIP(hipMemcpyAsync(raw_idx.p, indices, 8 * (size_t)nnz, hipMemcpyHostToDevice, s->st));
+      hipLaunchKernelGGL(k_narrow_idx, dim3(grid_e), dim3(256), 0, s->st, raw_idx.p, 8, nnz, G, (int32_t*)ridx.p, (int*)bad.p);
+    } else {
+      UP_HIP(hipMemcpyAsync(ridx.p, indices, 4 * (size_t)nnz, hipMemcpyHostToDevice, s->st));
+      hipLaunchKernelGGL(k_narrow_idx, dim3(grid_e), dim3(256), 0, s->st, ridx.p, 4, nnz, G, (int32_t*)ridx.p, (int*)bad.p);
+    }
+    UP_HIP(hipGetLastError());
+    UP_HIP(hipMemcpyAsync(raw_val.p, data, (size_t)(vb * nnz), hipMemcpyHostToDevice, s->st));
+    UP_HIP(hipMemcpyAsync(&bad_h, bad.p, 4, hipMemcpyDeviceToHost, s->st));
+    UP_HIP(hipStreamSynchronize(s->st));
+    if (bad_h) {
+      cleanup();
+      CNA_FAIL(CNA_EINVAL, "expression matrix: a column index lies outside [0, n_genes)");
+    }
+    if (raw_idx.p) buf_free(c, raw_idx);
+    // blocks of rows: at most 2048, and a counter table of at most 64M words
+    int64_t B = std::min<int64_t>(2048, std::max<int64_t>(1, (64ll << 20) / G));
+    B = std::min<int64_t>(B, n);
+    const int64_t rpb = (n + B - 1) / B;
+    B = (n + rpb - 1) / rpb;
+    UP_TRY(buf_need(c, s, cnt, 4 * B * G));
+    UP_TRY(buf_need(c, s, total, 8 * G));
+    UP_HIP(hipMemsetAsync(cnt.p, 0, (size_t)(4 * B * G), s->st));
+    hipLaunchKernelGGL(k_tr_count, dim3((unsigned)B), dim3(256), 0, s->st, (const int64_t*)rptr.p, (const int32_t*)ridx.p, n, G,
+                       rpb, (unsigned int*)cnt.p);
+    hipLaunchKernelGGL(k_tr_scan, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s->st, (unsigned int*)cnt.p, G, (int)B,
+                       (int64_t*)total.p);
+    UP_HIP(hipGetLastError());
+    std::vector<int64_t> tot((size_t)G);
+    UP_HIP(hipMemcpyAsync(tot.data(), total.p, 8 * (size_t)G, hipMemcpyDeviceToHost, s->st));
+    UP_HIP(hipStreamSynchronize(s->st));
+    gptr_h.assign((size_t)G + 1, 0);
+    for (int64_t g = 0; g < G; ++g) gptr_h[(size_t)g + 1] = gptr_h[(size_t)g] + tot[(size_t)g];
+    if (gptr_h[(size_t)G] != nnz) {
+      cleanup();
+      CNA_FAIL(CNA_EINVAL, "expression matrix: the transpose lost entries (internal error)");
+    }
+    UP_HIP(hipMemcpyAsync(s->gptr.p, gptr_h.data(), 8 * (size_t)(G + 1), hipMemcpyHostToDevice, s->st));
+    if (is_f64)
+      hipLaunchKernelGGL(k_tr_fill<double>, dim3((unsigned)B), dim3(256), 0, s->st, (const int64_t*)rptr.p, (const int32_t*)ridx.p,
+                         (const double*)raw_val.p, n, G, rpb, (unsigned int*)cnt.p, (const int64_t*)s->gptr.p,
+                         (int32_t*)s->gcell.p, (double*)s->gval.p);
+    else
+      hipLaunchKernelGGL(k_tr_fill<float>, dim3((unsigned)B), dim3(256), 0, s->st, (const int64_t*)rptr.p, (const int32_t*)ridx.p,
+                         (const float*)raw_val.p, n, G, rpb, (unsigned int*)cnt.p, (const int64_t*)s->gptr.p,
+                         (int32_t*)s->gcell.p, (float*)s->gval.p);
+    UP_HIP(hipGetLastError());
+    UP_HIP(hipStreamSynchronize(s->st));
+  }
+  if (is_csc) UP_HIP(hipMemcpyAsync(s->gptr.p, gptr_h.data(), 8 * (size_t)(G + 1), hipMemcpyHostToDevice, s->st));
+  cleanup();
+  CNA_TRY(build_chunks(c, s, gptr_h));
+  return 0;
+#undef UP_TRY
+#undef UP_HIP
+}
+
+template <typename T, int Q>
+int launch_dense_q(ExprState* s, bool shared, int nslab, int64_t slab_rows) {
+  const dim3 grid((unsigned)((s->G + 63) / 64), (unsigned)nslab);
+  if (shared)
+    hipLaunchKernelGGL((k_gc_dense<T, Q, true>), grid, dim3(64), 0, s->st, (const T*)s->X.p, s->n, s->G, slab_rows,
+                       (const double*)s->vtab.p, (const uint32_t*)s->vmask.p, (double*)s->part.p);
+  else
+    hipLaunchKernelGGL((k_gc_dense<T, Q, false>), grid, dim3(64), 0, s->st, (const T*)s->X.p, s->n, s->G, slab_rows,
+                       (const double*)s->vtab.p, (const uint32_t*)s->vmask.p, (double*)s->part.p);
+  return 0;
+}
+
+template <typename T, int Q>
+int launch_sparse_q(ExprState* s, bool shared) {
+  const dim3 grid((unsigned)((s->nchunks + 3) / 4));
+  if (shared)
+    hipLaunchKernelGGL((k_gc_sparse<T, Q, true>), grid, dim3(256), 0, s->st, (const int64_t*)s->chunk_lo.p,
+                       (const int32_t*)s->chunk_gene.p, (const int64_t*)s->gptr.p, s->nchunks, s->chunk_len,
+                       (const int32_t*)s->gcell.p, (const T*)s->gval.p, (const double*)s->vtab.p, (const uint32_t*)s->vmask.p,
+                       (double*)s->part.p);
+  else
+    hipLaunchKernelGGL((k_gc_sparse<T, Q, false>), grid, dim3(256), 0, s->st, (const int64_t*)s->chunk_lo.p,
+                       (const int32_t*)s->chunk_gene.p, (const int64_t*)s->gptr.p, s->nchunks, s->chunk_len,
+                       (const int32_t*)s->gcell.p, (const T*)s->gval.p, (const double*)s->vtab.p, (const uint32_t*)s->vmask.p,
+                       (double*)s->part.p);
+  return 0;
+}
+
+template <typename T>
+int launch_pass(ExprState* s, int Q, bool shared, int nslab, int64_t slab_rows) {
+  const bool dense = s->format == 1;
+  switch (Q) {
+    case 1: return dense ? launch_dense_q<T, 1>(s, shared, nslab, slab_rows) : launch_sparse_q<T, 1>(s, shared);
+    case 2: return dense ? launch_dense_q<T, 2>(s, shared, nslab, slab_rows) : launch_sparse_q<T, 2>(s, shared);
+    case 4: return dense ? launch_dense_q<T, 4>(s, shared, nslab, slab_rows) : launch_sparse_q<T, 4>(s, shared);
+    case 8: return dense ? launch_dense_q<T, 8>(s, shared, nslab, slab_rows) : launch_sparse_q<T, 8>(s, shared);
+    default: return dense ? launch_dense_q<T, 16>(s, shared, nslab, slab_rows) : launch_sparse_q<T, 16>(s, shared);
+  }
+}
+
+}  // namespace
+
+void expr_destroy(cna_ctx* c) {
+  ExprState* s = state_of(c);
+  if (!s) return;
+  release_matrix(c, s);
+  if (s->st) (void)hipStreamDestroy(s->st);
+  delete s;
+  c->expr = nullptr;
+}
+
+#define GC_CHECK_CTX(c)                                      \
+  do {                                                       \
+    if (!(c)) CNA_FAIL(CNA_EINVAL, "null context");          \
+    HIP_TRY(hipSetDevice((c)->device));                      \
+  } while (0)
+
+extern "C" {
+
+int cna_expr_drop(cna_ctx* c) {
+  GC_CHECK_CTX(c);
+  if (state_of(c)) release_matrix(c, state_of(c));
+  return 0;
+}
+
+int cna_expr_shape(cna_ctx* c, int64_t* n_cells, int64_t* n_genes, int64_t* nnz, int* format, int* is_f64, int64_t* n_uploads) {
+  GC_CHECK_CTX(c);
+  const ExprState* s = state_of(c);
+  if (n_cells) *n_cells = s ? s->n : 0;
+  if (n_genes) *n_genes = s ? s->G : 0;
+  if (nnz) *nnz = s ? s->nnz : 0;
+  if (format) *format = s ? s->format : 0;
+  if (is_f64) *is_f64 = s ? s->is_f64 : 0;
+  if (n_uploads) *n_uploads = s ? s->n_uploads : 0;
+  return 0;
+}
+
+int cna_expr_upload_dense(cna_ctx* c, const void* x, int64_t n_cells, int64_t n_genes, int is_f64) {
+  GC_CHECK_CTX(c);
+  if (!x) CNA_FAIL(CNA_EINVAL, "expression matrix: null pointer");
+  if (n_cells < 1 || n_genes < 1 || n_cells >= (1ll << 31) || n_genes >= (1ll << 31))
+    CNA_FAIL(CNA_EINVAL, "expression matrix: cells and genes must lie in [1, 2^31)");
+  ExprState* s = nullptr;
+  CNA_TRY(get_state(c, &s));
+  release_matrix(c, s);
+  const int64_t bytes = n_cells * n_genes * (is_f64 ? 8 : 4);
+  int rc = buf_need(c, s, s->X, bytes);
+  if (rc != 0) {
+    release_matrix(c, s);
+    if (rc == CNA_ENOMEM)
+      cna_set_error("expression matrix: " + std::to_string(bytes) + " bytes do not fit on the device; nothing is resident");
+    return rc;
+  }
+  hipError_t e = hipMemcpyAsync(s->X.p, x, (size_t)bytes, hipMemcpyHostToDevice, s->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->st);
+  if (e != hipSuccess) {
+    release_matrix(c, s);
+    cna_set_error(std::string("expression matrix upload: ") + hipGetErrorString(e));
+    return (int)e;
+  }
+  s->format = 1;
+  s->is_f64 = is_f64 != 0;
+  s->n = n_cells; s->G = n_genes; s->nnz = n_cells * n_genes;
+  s->n_uploads += 1;
+  return 0;
+}
+
+int cna_expr_upload_sparse(cna_ctx* c, const void* indptr, const void* indices, const void* data, int64_t n_cells,
+                           int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc) {
+  GC_CHECK_CTX(c);
+  if (!indptr || (nnz > 0 && (!indices || !data))) CNA_FAIL(CNA_EINVAL, "expression matrix: null pointer");
+  if (n_cells < 1 || n_genes < 1 || n_cells >= (1ll << 31) || n_genes >= (1ll << 31) || nnz < 0)
+    CNA_FAIL(CNA_EINVAL, "expression matrix: cells and genes must lie in [1, 2^31), nnz in [0, 2^63)");
+  if (index_bytes != 4 && index_bytes != 8) CNA_FAIL(CNA_EINVAL, "expression matrix: indices take 4 or 8 bytes");
+  ExprState* s = nullptr;
+  CNA_TRY(get_state(c, &s));
+  release_matrix(c, s);
+  const int rc = upload_sparse(c, s, indptr, indices, data, n_cells, n_genes, nnz, index_bytes, is_f64 != 0, is_csc != 0);
+  if (rc != 0) {
+    const std::string why = cna_last_error();
+    release_matrix(c, s);
+    if (rc == CNA_ENOMEM)
+      cna_set_error("expression matrix: the device has no room for the gene-major copy" +
+                    std::string(is_csc ? "" : " and the rows it is transposed from") + " (" + why + "); nothing is resident");
+    return rc;
+  }
+  s->format = 2;
+  s->n_uploads += 1;
+  return 0;
+}
+
+int cna_gene_corr(cna_ctx* c, const double* V, int q, double* r_out) {
+  GC_CHECK_CTX(c);
+  ExprState* s = state_of(c);
+  if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_gene_corr: no expression matrix is resident (cna_expr_upload_*)");
+  if (!V || !r_out) CNA_FAIL(CNA_EINVAL, "cna_gene_corr: null pointer");
+  if (q < 1 || q > GC_MAXQ) CNA_FAIL(CNA_EINVAL, "cna_gene_corr: 1 <= q <= 16 key columns");
+  int Q = 1;
+  while (Q < q) Q *= 2;
+  const int64_t n = s->n, G = s->G;
+  CNA_TRY(buf_need(c, s, s->vraw, 8 * n * q));
+  CNA_TRY(buf_need(c, s, s->vtab, 8 * n * Q));
+  CNA_TRY(buf_need(c, s, s->vmask, 4 * n));
+  CNA_TRY(buf_need(c, s, s->kstat, 8 * KS_LD * GC_MAXQ));
+  CNA_TRY(buf_need(c, s, s->flag, 256));
+  CNA_TRY(buf_need(c, s, s->rout, 8 * G * q));
+  HIP_TRY(hipMemcpyAsync(s->vraw.p, V, (size_t)(8 * n * q), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemsetAsync(s->flag.p, 0, 4, s->st));
+  hipLaunchKernelGGL(k_key_stats, dim3(q), dim3(1024), 0, s->st, (const double*)s->vraw.p, n, (double*)s->kstat.p);
+  hipLaunchKernelGGL(k_key_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, (const double*)s->vraw.p, n, q, Q,
+                     (const double*)s->kstat.p, (double*)s->vtab.p, (uint32_t*)s->vmask.p, (int*)s->flag.p);
+  HIP_TRY(hipGetLastError());
+  // keys that leave out the same cells (usually none) share the sums of x and x^2: one set instead of q
+  int differ = 0;
+  HIP_TRY(hipMemcpyAsync(&differ, s->flag.p, 4, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  const bool shared = differ == 0;
+  const int S = shared ? 1 : Q;
+  if (s->format == 1) {
+    const int F = 4 * S + Q;
+    // slabs: enough single-wave workgroups to fill the device, partial records at most ~2 % of the matrix' bytes
+    const int64_t gene_blocks = (G + 63) / 64;
+    int64_t nslab = std::min<int64_t>(2048, (8192 + gene_blocks - 1) / gene_blocks);
+    nslab = std::max<int64_t>(1, std::min<int64_t>(nslab, n / (100 * (int64_t)F)));
+    const int64_t slab_rows = (n + nslab - 1) / nslab;
+    nslab = (n + slab_rows - 1) / slab_rows;
+    CNA_TRY(buf_need(c, s, s->part, 8 * nslab * F * G));
+    if (s->is_f64) launch_pass<double>(s, Q, shared, (int)nslab, slab_rows);
+    else launch_pass<float>(s, Q, shared, (int)nslab, slab_rows);
+    hipLaunchKernelGGL(k_gc_finish_dense, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s->st, (const double*)s->part.p, G,
+                       (int)nslab, q, Q, S, (const double*)s->kstat.p, (double*)s->rout.p);
+  } else {
+    const int F = 5 * S + Q;
+    CNA_TRY(buf_need(c, s, s->part, 8 * std::max<int64_t>(1, s->nchunks) * F));
+    if (s->nchunks) {
+      if (s->is_f64) launch_pass<double>(s, Q, shared, 0, 0);
+      else launch_pass<float>(s, Q, shared, 0, 0);
+    }
+    hipLaunchKernelGGL(k_gc_finish_sparse, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s->st, (const double*)s->part.p,
+                       (const int64_t*)s->gchunk.p, G, q, Q, S, (const double*)s->kstat.p, (double*)s->rout.p);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(r_out, s->rout.p, (size_t)(8 * G * q), hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return 0;
+}
+
+}  // extern "C"

@@ -52,6 +52,7 @@ class Engine(_order.CellOrder):
         self._defer_graph_check = False
         self._graph_ref = None
         self._pinned = None
+        self._expr_key = self._expr_hash = self._expr_ref = self._expr_pinned = None
         self._host_threads = _order.usable_cpus(8)
         self._colsum_w = None
         self._codes_token = self._codes_graph = None
@@ -1102,6 +1103,115 @@ class Engine(_order.CellOrder):
               'cna_allgather_host')
         out = np.empty(int(sizes.sum()), dtype=np.int64)
         check(self.lib.cna_allgather_host(self.h, ptr(a), len(a), ptr(out), len(out)), 'cna_allgather_host')
+        return out
+
+    # ---------------------------------------------------------------- expression matrix (tools._genes.gene_corr)
+    @staticmethod
+    def _expr_arrays(X):
+        return (X,) if isinstance(X, np.ndarray) else (X.data, X.indices, X.indptr)
+
+    def _expr_buffers(self, X):
+        return tuple(a.ctypes.data for a in self._expr_arrays(X))
+
+    def _expr_ident(self, X):
+        if not isinstance(X, np.ndarray):
+            return (X.format,) + self._ident(X)
+        return ('dense', X.shape, str(X.dtype), id(X), X.ctypes.data)
+
+    def _expr_quick_key(self, X):
+        """Cheap identity of an expression matrix, like `_quick_key` of a graph (which serves the sparse formats as it
+        is): object, buffers, sizes, dtypes and a hash of three 64 KB windows.  Necessary, not sufficient."""
+        if not isinstance(X, np.ndarray):
+            return (X.format,) + self._quick_key(X)
+        flat = X.reshape(-1)
+        w = 16384
+        mid = max(0, flat.size // 2 - w // 2)
+        parts = [slice(0, w), slice(mid, mid + w), slice(max(0, flat.size - w), flat.size)]
+        return self._expr_ident(X) + tuple(self._hash(flat[p_], 1) for p_ in parts)
+
+    def _expr_is_pinned(self, X):
+        return (self._expr_pinned is not None and self._expr_pinned[0]() is X
+                and self._expr_pinned[1] == self._expr_buffers(X))
+
+    def pin_expression(self, X):
+        """Promise that the expression matrix X will not be edited in place while it is resident: later calls then
+        recognise it without hashing all of it (what a loop over many phenotypes of one dataset wants).
+        `unpin_expression()` withdraws the promise."""
+        if not isinstance(X, np.ndarray) and not sp.issparse(X):
+            raise TypeError('pin_expression needs the matrix that is passed to gene_corr')
+        self._expr_pinned = (weakref.ref(X), self._expr_buffers(X))
+
+    def unpin_expression(self):
+        self._expr_pinned = None
+
+    def drop_expression(self):
+        """Forget the resident expression matrix and free its device memory: the next call uploads afresh."""
+        self._expr_key = self._expr_hash = self._expr_ref = None
+        check(self.lib.cna_expr_drop(self.h), 'cna_expr_drop')
+
+    def ensure_expression(self, X):
+        """Upload the expression matrix (cells x genes, caller's cell order; already validated by tools._genes) unless
+        this very matrix -- same object, same content -- is resident.  Content check as for the graph: the full hash of
+        its arrays unless the matrix is pinned (`pin_expression`).  One matrix per engine: another one replaces it.
+        Returns True when it went to the device."""
+        same = self._expr_key is not None and self._expr_ref is not None and self._expr_ref() is X
+        pinned = self._expr_is_pinned(X)
+        if pinned and same:
+            # pinned: the caller's promise replaces the content probes
+            ident = self._expr_ident(X)
+            if self._expr_key[:len(ident)] == ident:
+                return False
+        quick = self._expr_quick_key(X)
+        full = None
+        if same and self._expr_key == quick:
+            if pinned:
+                return False
+            full = tuple(self._hash(a) for a in self._expr_arrays(X))
+            if full == self._expr_hash:
+                return False
+        self._expr_key = self._expr_hash = self._expr_ref = None
+        self._upload_expression(X)
+        self._expr_key = quick
+        self._expr_hash = full if full is not None else tuple(self._hash(a) for a in self._expr_arrays(X))
+        try:
+            self._expr_ref = weakref.ref(X)
+        except TypeError:
+            self._expr_ref = None
+        return True
+
+    def _upload_expression(self, X):
+        n, g = X.shape
+        if isinstance(X, np.ndarray):
+            check(self.lib.cna_expr_upload_dense(self.h, ptr(X), n, g, int(X.dtype == np.float64)), 'cna_expr_upload_dense')
+        else:
+            M = X
+            if not M.has_canonical_format:
+                # duplicates add up and indices ascend, as toarray() would have it (a copy: the caller's matrix stays)
+                M = M.copy()
+                M.sum_duplicates()
+            idt = np.int32 if M.indices.dtype == np.int32 and M.indptr.dtype == np.int32 else np.int64
+            indptr = np.ascontiguousarray(M.indptr, dtype=idt)
+            indices = np.ascontiguousarray(M.indices, dtype=idt)
+            data = np.ascontiguousarray(M.data)
+            check(self.lib.cna_expr_upload_sparse(self.h, ptr(indptr), ptr(indices), ptr(data), n, g, int(M.nnz),
+                                                  indptr.dtype.itemsize, int(data.dtype == np.float64),
+                                                  int(M.format == 'csc')), 'cna_expr_upload_sparse')
+
+    def expression_shape(self):
+        """What is resident: dict(n_cells, n_genes, nnz, format 'none' | 'dense' | 'gene-major', f64, uploads)."""
+        n, g, nnz, up = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        fmt, f64 = C.c_int(0), C.c_int(0)
+        check(self.lib.cna_expr_shape(self.h, C.byref(n), C.byref(g), C.byref(nnz), C.byref(fmt), C.byref(f64), C.byref(up)),
+              'cna_expr_shape')
+        return dict(n_cells=n.value, n_genes=g.value, nnz=nnz.value, format=('none', 'dense', 'gene-major')[fmt.value],
+                    f64=bool(f64.value), uploads=up.value)
+
+    def gene_corr(self, V):
+        """Pearson correlation of every gene of the resident expression matrix with every row of V (q x cells float64,
+        caller's cell order, NaN = cell left out): q x genes float64 (cna_gene_corr)."""
+        V = _f64(V)
+        out = np.empty((V.shape[0], self.expression_shape()['n_genes']))
+        check(self.lib.cna_gene_corr(self.h, ptr(V), V.shape[0], ptr(out)), 'cna_gene_corr')
         return out
 
     # ---------------------------------------------------------------- synthetic inputs

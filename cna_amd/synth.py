@@ -23,10 +23,18 @@ class CellData:
     (or ``data.uns['neighbors']['connectivities']``) -- /root/reference/src/cna/tools/_nam.py:12-19.
     """
 
-    def __init__(self, obs, connectivities):
+    def __init__(self, obs, connectivities, X=None, var=None, layers=None):
         self.obs = obs
         self.obsp = {'connectivities': connectivities}
         self.uns = {'neighbors': {'connectivities': connectivities}}
+        # optional, for cna.tl.gene_corr: expression (cells x genes), per-gene frame, named alternatives of X
+        self.X = X
+        self.var = var
+        self.layers = {} if layers is None else layers
+
+    @property
+    def var_names(self):
+        return None if self.var is None else self.var.index
 
     @property
     def n_obs(self):
@@ -213,7 +221,7 @@ def make_dataset(n_cells, n_samples, k=30, seed=0, dim=8, n_clusters=20,
 
 
 def make_demo_like(n_samples=50, n_genes=50, cells_per_sample=200, noise=1.0, k=15, seed=0,
-                   graph_dtype=np.float32):
+                   graph_dtype=np.float32, keep_expression=False):
     """The reference's demo dataset, regenerated (recipe: /root/reference/demo/makedata.ipynb cells 2-4):
     `n_samples` samples of `cells_per_sample` cells over `n_genes` genes, three cell populations whose
     per-sample proportions depend on the sample-level covariates `case` and `male`, five batches
@@ -221,6 +229,9 @@ def make_demo_like(n_samples=50, n_genes=50, cells_per_sample=200, noise=1.0, k=
     numpy's legacy generator seeded with `seed`, in the notebook's order.  The notebook then calls
     scanpy.pp.neighbors (not installed here): the graph below is this module's own fuzzy kNN stand-in
     on the expression matrix (k = scanpy's default 15), so the dataset is demo-LIKE, not the demo.
+
+    keep_expression=True also attaches that expression matrix as ``data.X`` (float32, cells x genes) and a ``data.var``
+    frame indexed by gene name, as the demo's AnnData has them (what cna.tl.gene_corr reads).
 
     Returns (data, samplem) with samplem a DataFrame indexed by sample id with columns case, male, batch."""
     N, G, C = int(n_samples), int(n_genes), int(cells_per_sample)
@@ -248,4 +259,8 @@ def make_demo_like(n_samples=50, n_genes=50, cells_per_sample=200, noise=1.0, k=
     A = fuzzy_knn_graph(X, k=k, dtype=graph_dtype)
     obs = pd.DataFrame({'id': np.repeat(samplem.index.values, C)},
                        index=pd.Index(['cell_%d' % i for i in range(N * C)], name='cell'))
-    return CellData(obs, A), samplem
+    data = CellData(obs, A)
+    if keep_expression:
+        data.X = X
+        data.var = pd.DataFrame(index=pd.Index(['gene_%d' % g for g in range(G)], name='gene'))
+    return data, samplem

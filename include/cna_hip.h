@@ -570,6 +570,48 @@ int  cna_host_permute_rows(const int64_t* perm, int64_t r0, int64_t r1, const in
 int  cna_knn_graph(cna_ctx* ctx, const float* X, int64_t n, int d, int k, int64_t* indptr_out,
                    int32_t* indices_out, float* data_out, int64_t* nnz_out);
 
+/* ---- per-gene correlation to per-cell columns (csrc/genes.hip) ------------------------------ */
+/* The step of the reference's workflow that follows cna.tl.association (demo/demo.ipynb, "per-gene correlations to
+ * neighborhood coefficient"):
+ *     d.var['corr_case'] = np.corrcoef(d.obs.male_coef.values.reshape(1,-1), d.X, rowvar=False)[0,1:]
+ * with the expression matrix d.X resident on the device.  One matrix per context, in the CALLER's cell order; it is
+ * derived from nothing else the context holds (graph, walk, NAM, working matrix, device cell order) and nothing else is
+ * derived from it, so these entry points may be called at any point of an analysis -- also between the launch and the
+ * fetch of a local-null pass -- and work on a context that never saw a graph.  They use a stream of their own. */
+
+/* d.X of that line as a C-contiguous n_cells x n_genes array, float32 or float64 (demo/demo.ipynb, "per-gene
+ * correlations to neighborhood coefficient").  Replaces the resident matrix, if any.  1 <= n_cells, n_genes < 2^31.
+ * CNA_ENOMEM: it does not fit; the context then holds no expression matrix. */
+int  cna_expr_upload_dense(cna_ctx* ctx, const void* x, int64_t n_cells, int64_t n_genes, int is_f64);
+/* The same d.X as a scipy CSR (is_csc = 0: indptr has n_cells + 1 entries, indices are genes) or CSC (is_csc = 1:
+ * n_genes + 1 entries, indices are cells) matrix, which np.corrcoef of that line (demo/demo.ipynb, "per-gene
+ * correlations to neighborhood coefficient") cannot take at all.  index_bytes: 4 or 8, for indptr and indices alike;
+ * values float32 or float64; nnz < 2^63.  Canonical form is expected (indices ascending inside a row / column, no
+ * duplicates -- what scipy's sum_duplicates() leaves; explicit zeros may stay).  The device keeps gene-major lists
+ * {cell, value}, cells ascending: a CSC upload is that already, a CSR upload is transposed on the device by counting
+ * (stable in the cell index, so both give the same lists and the same bits later).  The transpose needs the rows'
+ * indices and values beside the result for a moment: CNA_ENOMEM, with nothing resident afterwards, when that does
+ * not fit.  CNA_EINVAL: offsets that do not start at 0 / fall / end elsewhere than nnz, or an index out of range. */
+int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indices, const void* data, int64_t n_cells,
+                            int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
+/* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
+ * work buffers of cna_gene_corr: cna_ctx_device_bytes returns to what it was before the upload. */
+int  cna_expr_drop(cna_ctx* ctx);
+/* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
+ * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
+int  cna_expr_shape(cna_ctx* ctx, int64_t* n_cells, int64_t* n_genes, int64_t* nnz, int* format, int* is_f64,
+                    int64_t* n_uploads);
+/* r_out[j * n_genes + g] = Pearson correlation of gene g of the resident matrix with column j of V (q x n_cells
+ * row-major, caller's cell order, 1 <= q <= 16) over the cells where V[j] is finite -- each column has its own such
+ * set; NaN marks the cells cna.tl.association did not keep.  With every cell finite this is row 0 of
+ * np.corrcoef(v, X, rowvar=False) without its first entry (demo/demo.ipynb, "per-gene correlations to
+ * neighborhood coefficient"), computed in one pass over X instead of a (genes + 1)^2 matrix: per gene the sums of x,
+ * x^2 and x (v - mean v), float64, in a fixed order (no floating-point atomics: the same bits on every run).  NaN
+ * where numpy's 0 / 0 gives NaN: a gene that is constant over the column's cells, decided exactly (minimum ==
+ * maximum), a constant column, fewer than two finite cells; NaN / inf inside X reach that gene's result.
+ * CNA_ESTATE: no expression matrix is resident. */
+int  cna_gene_corr(cna_ctx* ctx, const double* V, int q, double* r_out);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
  * on = 2: the walk kernels (CNA_K_NAM_FIRST / _STEP / _STEP_SPARSE) and the communication spans only -- two event records
