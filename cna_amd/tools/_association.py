@@ -13,6 +13,7 @@ Same call surface, result fields, warnings and error behaviour as the reference'
                                           data.obs columns incl. the per-cell FDR lookup (:230-237)
 """
 import os
+import threading
 import warnings
 
 import numpy as np
@@ -23,10 +24,12 @@ from .. import _ffi
 from ..engine import get_engine
 from ._nam import (LazyNamespace, _nam_device, _qc_device, _resid_plan, _resid_run, sample_codes_cached, confirm_codes,
                    shard_of, global_samples, get_connectivity,
-                   _small_svd, _defer_pcs, host_blas_threads, _top_pcs, GramPCs)
+                   _small_svd, host_blas_threads, _top_pcs, GramPCs)
 from . import _nam as _nam_mod
 from . import _fast
+from . import _result
 from ._out import select_output
+from ._result import holds_last_step
 from ._stats import conditional_permutation, grouplevel_permutation, default_ks, minp_stats, native_draw_start
 
 
@@ -55,11 +58,18 @@ _PREFETCH_GRAPH = True    # a new graph's upload beside the factorisation of the
 _PREFETCH_CELLS = 100_000
 _NATIVE_DRAW = True       # the draw on the library's host thread (False: the interpreter's helper thread; tests patch it)
 _SWITCH_INTERVAL = 5e-5   # GIL hand-over between the helper thread and this one: 2.08 -> 1.86 ms per call at 200k cells (default interval: 5 ms)
+_FUSE = True
+_TRACE = None      # list of (label, perf_counter) when tools/host_trace.py switches tracing on
+_COEF_FIRST_CELLS = 500000
+# From this many cells on (and three or more steps) the walk's last step is queued after validation and planning, which
+# run under the first steps; it then knows what the selection pass will be asked for and does it on its way out
+# (compute_nam_and_reindex).  Below, the first steps are too short to hide the host work.
+# (150 000: at 250 000 cells x 200 samples -- a rank's block of the 2M problem on eight GPUs -- the by-product saves the
+# selection pass, 4.23-4.48 -> 4.01-4.29 ms; at 200 000 x 50 it is neutral, 1.60 -> 1.58; it was 300 000 before round 4's
+# last day.)  Sharded inputs: the size of the largest block, the same number on every rank.
+_DEFER_LAST_CELLS = int(os.environ.get('CNA_DEFER_LAST_CELLS', '150000'))
 
-
-import threading as _threading
-
-_switch_lock = _threading.Lock()
+_switch_lock = threading.Lock()
 _switch_users = 0
 _switch_saved = None
 
@@ -110,26 +120,6 @@ class _InlineJob:
 
     def exception(self):
         return None
-_FUSE = True
-
-_TRACE = None      # list of (label, perf_counter) when tools/host_trace.py switches tracing on
-
-
-_COEF_FIRST_CELLS = 500000
-# From this many cells on (and three or more steps) the walk's last step is queued after validation and planning, which
-# run under the first steps; it then knows what the selection pass will be asked for and does it on its way out
-# (compute_nam_and_reindex).  Below, the first steps are too short to hide the host work.
-# (150 000: at 250 000 cells x 200 samples -- a rank's block of the 2M problem on eight GPUs -- the by-product saves the
-# selection pass, 4.23-4.48 -> 4.01-4.29 ms; at 200 000 x 50 it is neutral, 1.60 -> 1.58; it was 300 000 before round 4's
-# last day.)  Sharded inputs: the size of the largest block, the same number on every rank.
-_DEFER_LAST_CELLS = int(os.environ.get('CNA_DEFER_LAST_CELLS', '150000'))
-
-
-def _rule_cells(data, engine):
-    shard = getattr(data, 'uns', {}).get('cna_shard') if hasattr(data, 'uns') else None
-    if shard:
-        return -(-int(shard['n_global']) // max(1, int(getattr(engine, 'nranks', 1))))
-    return len(data.obs)
 
 
 def _host_copy(dst, src):
@@ -398,56 +388,22 @@ def _association(engine, res, y, y_, ks=None, Nnull=1000, local_test=True, show_
 
     if not tail_first:
         _mark('null fetched')
-    if (best < 0).any():
-        raise ValueError('All-NaN slice encountered')        # np.nanargmin in _minp_stats
-    k, p, r2 = ks[best[0]], pv[0], r2v[0]
-    if k == max(ks):
-        warnings.warn(('data supported use of {} NAM PCs, which is the maximum considered. ' +
-                       'Consider allowing more PCs by using the "ks" argument.').format(k))
-
-    # coefficients and r2 of the chosen model
-    ycond_v = Mv.dot(y)
-    ycond_v = ycond_v / ycond_v.std(ddof=1)
-    beta_k = Uk[:, :k].T.dot(ycond_v)                   # up to the sign of every PC
-    yhat = Uk[:, :k].dot(beta_k)                         # sign free
-    r2_perpc = (beta_k / np.sqrt(ycond_v.dot(ycond_v))) ** 2
-
-    # sample-space frames of the result are only built when somebody reads them; what shows the PC signs
-    # (U, beta) comes from LAPACK's SVD of G like upstream's (_nam.py:105, _association.py:70-72)
-    nU = len(G)
-
-    def _names():
-        return ['PC' + str(i) for i in range(1, nU + 1)]
-    res._defer('namresid_sampleXpc', lambda: pd.DataFrame(pcs.U, index=M.index, columns=_names()))
-    res._defer('namresid_svs', lambda: pd.Series(pcs.svs, index=_names())[:npcs if npcs is not None else nU])
-    res._defer('namresid_varexp', lambda: pd.Series(pcs.svs, index=_names()) / nU / (n_cells() if callable(n_cells) else n_cells))
-    res._defer('yresid', lambda: pd.Series(ycond_v, index=getattr(M, 'index', None)))
-    res._defer('beta', lambda: pcs.U[:, :k].T.dot(ycond_v))
-
-    nullminps, nullr2s = pv[1:], r2v[1:]
-    hits = (nullminps <= p + 1e-8).sum()
-    pfinal = (hits + 1) / (Nnull + 1)
-    if hits == 0:
-        warnings.warn('global association p-value attained minimal possible value. ' +
-                      'Consider increasing Nnull')
-
-    fdr_vals = None
-    fdr_5p_t = fdr_10p_t = None
+    found = _result.verdict(best, pv, r2v, ks, Nnull)
+    fdrs = fdr_5p_t = fdr_10p_t = runmin = None
     if local_test:
         print('computing neighborhood-level FDRs', file=out)
         if early_tail is not None and early_tail[0] == 'error':
             raise early_tail[1]
         fdr_vals, fdr_5p_t, fdr_10p_t, runmin = early_tail[1] if early_tail is not None else \
             _fdr_tables(tail_sums, ranks, Nloc, thresholds)
-        res._defer('fdrs', lambda: pd.DataFrame({'threshold': thresholds, 'fdr': fdr_vals,
-                                                 'num_detected': num_detected}))
-    else:
-        res.fdrs = None
+        fdrs = (thresholds, fdr_vals, num_detected)
+    # sample-space frames of the result are only built when somebody reads them
+    _result.sample_fields(res, pcs, Uk, Mv, y, M.index, ks, npcs, n_cells, found, fdrs, fdr_5p_t, fdr_10p_t)
 
     # data.obs columns (all cells) and, from them, the coefficients of the kept cells
     if early_tail is not None:
         coef_all, fdr_all = early_tail[2]
-    elif fdr_vals is not None:
+    elif fdrs is not None:
         _mark('pre percell')
         coef_all, fdr_all = engine.percell(thresholds, runmin)
     else:
@@ -455,10 +411,6 @@ def _association(engine, res, y, y_, ks=None, Nnull=1000, local_test=True, show_
 
     if early_tail is None:
         _mark('percell done')
-    res.__dict__.update({'p': pfinal, 'nullminps': nullminps, 'k': k, 'fdr_5p_t': fdr_5p_t,
-                         'fdr_10p_t': fdr_10p_t, 'yresid_hat': yhat, 'ks': ks,
-                         'r2': r2, 'r2_perpc': r2_perpc, 'nullr2_mean': nullr2s.mean(),
-                         'nullr2_std': nullr2s.std()})
     return coef_all, fdr_all, pcs
 
 
@@ -709,7 +661,7 @@ def association(data, y, sid_name, batches=None, covs=None, donorids=None, ks=No
         # the fixed-shape call (nsteps given, one batch, a seed, ...) in two library calls (tools/_fast.py); everything
         # else -- and whatever that path meets and does not handle -- goes on below as if it did not exist
         out = _fast.association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_frac_pcs, nsteps, show_progress,
-                                allow_low_sample_size, return_full, ridges, eng, kwargs)
+                                allow_low_sample_size, return_full, ridges, eng, kwargs, _DEFER_LAST_CELLS, _fdr_tables)
         if out is not _fast.NOT_TAKEN:
             return out
         # The resident graph is validated by a hash of its full content (engine.ensure_graph).  On one GPU
@@ -729,26 +681,25 @@ def association(data, y, sid_name, batches=None, covs=None, donorids=None, ks=No
 
 def _association_attempts(eng, rng_state, data, y, sid_name, batches, covs, donorids, ks, key_added, max_frac_pcs, nsteps,
                           show_progress, allow_low_sample_size, return_full, ridges, kwargs):
-    for _once in (0,):
-        for attempt in (0, 1):
-            eng._defer_graph_check = attempt == 0 and hasattr(eng, 'confirm_graph')
-            try:
-                return _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added, max_frac_pcs, nsteps,
-                                         show_progress, allow_low_sample_size, return_full, ridges, eng, **kwargs)
-            except _StaleGraph:
-                if rng_state is not None:
-                    np.random.set_state(rng_state)
-            except Exception:
-                # an error of the optimistic attempt counts only if its inputs were what the memos said
-                stale = not confirm_codes()
-                stale = (hasattr(eng, 'confirm_graph') and not eng.confirm_graph()) or stale
-                if attempt == 1 or not stale:
-                    raise
-                if rng_state is not None:
-                    np.random.set_state(rng_state)
-            finally:
-                eng._defer_graph_check = False
-        raise RuntimeError('the connectivities matrix keeps changing while it is being analysed')
+    for attempt in (0, 1):
+        eng._defer_graph_check = attempt == 0 and hasattr(eng, 'confirm_graph')
+        try:
+            return _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added, max_frac_pcs, nsteps,
+                                     show_progress, allow_low_sample_size, return_full, ridges, eng, **kwargs)
+        except _StaleGraph:
+            if rng_state is not None:
+                np.random.set_state(rng_state)
+        except Exception:
+            # an error of the optimistic attempt counts only if its inputs were what the memos said
+            stale = not confirm_codes()
+            stale = (hasattr(eng, 'confirm_graph') and not eng.confirm_graph()) or stale
+            if attempt == 1 or not stale:
+                raise
+            if rng_state is not None:
+                np.random.set_state(rng_state)
+        finally:
+            eng._defer_graph_check = False
+    raise RuntimeError('the connectivities matrix keeps changing while it is being analysed')
 
 
 class _StaleGraph(Exception):
@@ -805,7 +756,6 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
     # sample-level inputs, which then runs under it.  An error of the walk is held back until validation has
     # had its say -- the order in which the reference would have raised; with progress output the reference's
     # order of lines is kept instead (validation messages, then 'computing NAM').
-    import threading
     walk_queued = threading.Event()
     nam_queued = nam_error = None
     # (the checks that need no look at the data come first: a call with an argument of the wrong type neither starts a
@@ -816,8 +766,8 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         try:
             nam_queued = _nam_device(engine, data, sid_name, nsteps=nsteps, show_progress=False,
                                      codes_labels=(codes, labels, counts, token),
-                                     defer_last=(nsteps is not None and nsteps >= 3 and kwargs.get('local_test', True)
-                                                 and _rule_cells(data, engine) >= _DEFER_LAST_CELLS))
+                                     defer_last=(nsteps is not None and holds_last_step(data, engine, nsteps, len(labels), _DEFER_LAST_CELLS)
+                                                 and kwargs.get('local_test', True)))
         except Exception as exc:             # noqa: BLE001 - re-raised below, after validation
             nam_error = exc
         finally:
@@ -936,6 +886,15 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
             null_future.run()
         return plan
 
+    def stop_draw():
+        # on an error: do not leave the helper thread running, nor the library's draw uncollected (the reference fails
+        # before it seeds, _association.py:15-16: numpy's generator stays as it was), nor a local null the fused
+        # selection call launched
+        null_future.cancel() or null_future.exception()
+        if native is not None:
+            native.abandon()
+        _drop_pending_null(engine)
+
     engine._on_walk_queued = walk_queued.set
     try:
         kept, sample_index, colmap, batches, covs, donorids, filter_samples, plan = \
@@ -950,11 +909,8 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
                                                     and not getattr(engine, '_has_comm', False)) else None))
     except BaseException:
         walk_queued.set()
-        null_future.cancel() or null_future.exception()     # do not leave the helper thread running
-        if native is not None:
-            native.abandon()                                # ... nor the library's draw uncollected (the reference fails before
-        _drop_pending_null(engine)                          #     it seeds, _association.py:15-16: numpy's generator stays as it was)
-        raise                                               # (... nor a local null the fused selection call launched)
+        stop_draw()
+        raise
     finally:
         engine._on_walk_queued = None
         walk_queued.set()
@@ -967,14 +923,11 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
     N = filter_samples.sum()
     try:
         # (raises for a tuple ks, or an ndarray of more than two: the draw and its helper are then stopped below)
-        npcs = min(N, max([10] + [int(max_frac_pcs * N)] + [ks if ks is not None else []][0]))
+        npcs = _result.kept_pcs(N, max_frac_pcs, ks)
         res = _resid_run(engine, plan, cell_index, show_progress=show_progress)
     except BaseException:
-        null_future.cancel() or null_future.exception()     # do not leave the helper thread running
-        if native is not None:
-            native.abandon()                                # ... nor the library's draw uncollected (the reference fails before
-        _drop_pending_null(engine)                          #     it seeds, _association.py:15-16: numpy's generator stays as it was)
-        raise                                               # (... nor a local null the fused selection call launched)
+        stop_draw()
+        raise
 
     _mark('resid queued')
     print('performing association test', file=out)
@@ -987,17 +940,14 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
     # of the F-test call); should the test still fail, the column is put back as it was, so that --
     # like upstream -- an exception leaves data.obs alone
     early_coef = {}
-    had_key = key_added in data.obs
-    previous = data.obs[key_added] if had_key else None
+    fdr_key = f'{key_added}_fdr'
+    snap = _result.ObsSnapshot(data.obs, key_added, fdr_key)
 
     def confirm_graph():
         ok = confirm_codes()
         if (hasattr(engine, 'confirm_graph') and not engine.confirm_graph()) or not ok:
             raise _StaleGraph()
 
-    fdr_key = f'{key_added}_fdr'
-    had_fdr = fdr_key in data.obs
-    previous_fdr = data.obs[fdr_key] if had_fdr else None
     big = len(data.obs) >= _COEF_FIRST_CELLS
 
     def fdr_copied_early():
@@ -1013,16 +963,11 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         # put data.obs back as it was: nothing written by this call -- early or late -- outlives an exception
         # (or a stale attempt); like upstream, whose two assignments are the last statements that can fail
         fdr_copied_early()                                # the helper is done with the column's storage
-        if early_coef.pop('written', False):
-            if had_key:
-                data.obs[key_added] = previous
-            elif key_added in data.obs:
-                del data.obs[key_added]
-            if 'fdr_view' in early_coef or early_coef.get('fdr_touched') or (big and fdr_key in data.obs and not had_fdr):
-                if had_fdr:
-                    data.obs[fdr_key] = previous_fdr
-                elif fdr_key in data.obs:
-                    del data.obs[fdr_key]
+        if snap.written:
+            snap.written = False
+            snap.put_back(key_added)
+            if 'fdr_view' in early_coef or early_coef.get('fdr_touched') or (big and fdr_key in data.obs and not snap.had(fdr_key)):
+                snap.put_back(fdr_key)
             early_coef.pop('fdr_view', None)
             early_coef.pop('fdr_touched', None)
             early_coef.pop('fdr_done', None)
@@ -1030,7 +975,7 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
 
     def write_coef_early(coef):
         confirm_graph()                                   # nothing reaches data.obs from a stale graph
-        early_coef['written'] = True
+        snap.written = True
         data.obs[key_added] = coef
         early_coef['values'] = data.obs[key_added].values
         if big:
@@ -1053,7 +998,7 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         if 'values' not in early_coef or early_coef.get('fdr_view') is not None or fdr is None:
             return
         confirm_graph()
-        early_coef['written'] = early_coef['fdr_touched'] = True
+        snap.written = early_coef['fdr_touched'] = True
         data.obs[fdr_key] = fdr
         early_coef['fdr_done'] = True
 
@@ -1068,20 +1013,7 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
                                                  coef_launched=getattr(plan, 'coef_launched', False))
         _mark('_association returned')
         confirm_graph()                               # (stale: the retry starts from the frame as the caller left it)
-        _defer_pcs(res, engine, pcs, cell_index)
-        res.kept = kept
-
-        def fetch_nam():
-            if engine.nam_epoch != nam_epoch:
-                raise RuntimeError('res.nam lives on the GPU and a later cna_amd call has replaced it; '
-                                   'read it (or call res.materialize()) before running the next analysis')
-            return pd.DataFrame(engine.nam_full(keep=kept, cols=colmap, transposed=True), index=sample_index,
-                                columns=cell_index(), copy=False)
-
-        res._defer('nam', fetch_nam)
-        _mark('lazies set')
-
-        if had_key:
+        if snap.had(key_added):
             warnings.warn(f"Key '{key_added}' already exists in data.obs. Overwriting.")
         _mark('warned')
         # coef_all / fdr_all may be views of the engine's pinned buffers: the DataFrame stores its own
@@ -1089,13 +1021,14 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         if 'values' in early_coef:
             coef_kept = early_coef['values']                 # written while the null kernel was running
         else:
-            early_coef['written'] = True                  # (roll_back undoes a late write as well)
+            snap.written = True                           # (roll_back undoes a late write as well)
             data.obs[key_added] = coef_all
             coef_kept = data.obs[key_added].values
         if np.may_share_memory(coef_kept, coef_all):
             coef_kept = np.array(coef_all)
-        res._defer('ncorrs', lambda: pd.Series(coef_kept if kept.all() else coef_kept[kept], index=cell_index()))
         _mark('coef written')
+        _result.cell_fields(res, engine, pcs, kept, colmap, sample_index, cell_index, nam_epoch, coef_kept)
+        _mark('lazies set')
         view = early_coef.get('fdr_view')
         early = fdr_copied_early()
         if fdr_all is None:
@@ -1108,7 +1041,7 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
                 and fdr_all.shape == view.shape and fdr_key in data.obs and np.shares_memory(data.obs[fdr_key].values, view)):
             _host_copy(view, fdr_all)
         else:
-            early_coef['written'] = early_coef['fdr_touched'] = True
+            snap.written = early_coef['fdr_touched'] = True
             data.obs[fdr_key] = fdr_all
         _mark('obs written')
     except BaseException:
@@ -1123,8 +1056,7 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         raise AttributeError("'NoneType' object has no attribute 'loc'")
 
     if return_full:
-        # everything but the three cells x samples frames is materialised now, like upstream
-        for name in ('ncorrs', 'fdrs', 'namresid_sampleXpc', 'namresid_svs', 'namresid_varexp', 'yresid', 'beta'):
+        for name in _result.FULL_FIELDS:
             getattr(res, name)
         return res
     return res.p

@@ -27,10 +27,13 @@ import numpy as np
 import pandas as pd
 
 from .. import _ffi
-from ._nam import (LazyNamespace, GramPCs, _NO_NAM, _defer_pcs, _lowrank_ok, _prepare_graph, _resid_plan, _still_resident,
+from .._order import usable_cpus
+from . import _result
+from ._nam import (LazyNamespace, GramPCs, _NO_NAM, _lowrank_ok, _prepare_graph, _resid_plan, _still_resident,
                    _top_pcs, _walk_start, confirm_codes, eig_stats, get_connectivity, global_samples, host_blas_threads,
                    sample_codes_cached, shard_of)
 from . import _nam as _nam_mod
+from ._result import _rule_cells, holds_last_step
 from ._stats import default_ks, seeded_draw
 
 ENABLED = os.environ.get('CNA_ONE_CALL', '1') not in ('0', 'off', 'no')     # 0: every call takes the general path (A/B runs, tests)
@@ -38,7 +41,6 @@ NOT_TAKEN = object()
 stats = {'taken': 0, 'not_eligible': 0, 'general': 0, 'need_pcs': 0, 'stale': 0}
 _BIG_CELLS = 500000          # from here on: the coefficient column is copied before the Gram matrix is waited for, on several threads
 _eyes = {}
-_cpus = None
 _TRACE = None      # list of (label, perf_counter) when tools/host_trace.py switches tracing on
 
 
@@ -48,35 +50,14 @@ def _mark(label):
         _TRACE.append((label, time.perf_counter()))
 
 
+# (threads: this process's share of the host's CPUs as it is now -- _order.usable_cpus follows a later dist.init())
 def _copy_threads(n):
-    global _cpus
-    if n < _BIG_CELLS:
-        return 1
-    if _cpus is None:
-        from .._order import usable_cpus
-        _cpus = usable_cpus(8)
-    return min(8, _cpus)
-
-
-def _defer_last_cells():
-    from ._association import _DEFER_LAST_CELLS
-    return _DEFER_LAST_CELLS
-
-
-def _rule_cells(data, engine):
-    from ._association import _rule_cells as rule
-    return rule(data, engine)
+    return 1 if n < _BIG_CELLS else usable_cpus(8)
 
 
 def _draw_threads(normals):
     """(what tools/_stats.py:native_draw_start gives a draw of this size)"""
-    global _cpus
-    if normals < 80_000:
-        return 1
-    if _cpus is None:
-        from .._order import usable_cpus
-        _cpus = usable_cpus(8)
-    return min(4, _cpus)
+    return 1 if normals < 80_000 else usable_cpus(4)
 
 
 def _eye(N):
@@ -130,8 +111,9 @@ def _eligible(data, y, batches, covs, donorids, ks, nsteps, show_progress, engin
 
 
 def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_frac_pcs, nsteps, show_progress,
-                allow_low_sample_size, return_full, ridges, engine, kwargs):
-    """-> NOT_TAKEN, or what cna.tl.association returns (p, or the result namespace)."""
+                allow_low_sample_size, return_full, ridges, engine, kwargs, defer_last_cells, fdr_tables):
+    """-> NOT_TAKEN, or what cna.tl.association returns (p, or the result namespace).  ``defer_last_cells``, ``fdr_tables``:
+    the general path's own _DEFER_LAST_CELLS and _fdr_tables as they are at this call (tests patch them there)."""
     if not _eligible(data, y, batches, covs, donorids, ks, nsteps, show_progress, engine, kwargs):
         stats['not_eligible'] += 1
         return NOT_TAKEN
@@ -180,9 +162,8 @@ def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_f
             _mark('graph')
             sig, held = _walk_start(engine, codes, labels, counts, token, nsteps, 15, 1, False)
             walk = held is _NO_NAM
-            # (the last step leaves the selection pass's results on its way out under the general path's own rule -- wide
-            # sample axis, a block of 150 000 cells or more, _association.py:_DEFER_LAST_CELLS -- so that both paths run the
-            # same kernels)
+            # (the last step leaves the selection pass's results on its way out under the rule the general path follows
+            # -- wide sample axis, a block of 150 000 cells or more: _result.holds_last_step)
             if nsteps is None:
                 # the reference's default: walk until the median kurtosis stops falling (_nam.py:64-68); medians and rule on
                 # the device, the first steps queued ahead of the verdict, which the selection pass collects
@@ -192,7 +173,7 @@ def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_f
                     engine._nam_sig = (sig, engine.nam_epoch, None) if sig is not None else None
                 W_.update(sig=sig, walk=False, may_hint=False, early=0)
                 return
-            may_hint = walk and covs is None and N_all > 64 and nsteps >= 3 and _rule_cells(data, engine) >= _defer_last_cells()
+            may_hint = walk and covs is None and holds_last_step(data, engine, nsteps, N_all, defer_last_cells)
             early = (nsteps - 1 if may_hint else nsteps) if walk else 0
             if early:
                 engine.assoc_begin_part(0, early, nsteps)
@@ -261,23 +242,11 @@ def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_f
     sig, walk, may_hint, early = W_['sig'], W_['walk'], W_['may_hint'], W_['early']
 
     fdr_key = f'{key_added}_fdr'
-    had_key, had_fdr = key_added in data.obs, fdr_key in data.obs
-    previous = data.obs[key_added] if had_key else None
-    previous_fdr = data.obs[fdr_key] if had_fdr else None
-    touched = [False]
-
-    def roll_back():
-        # nothing written by this call outlives an exception or a detour through the general path
-        if touched[0]:
-            touched[0] = False
-            for key, had, prev in ((key_added, had_key, previous), (fdr_key, had_fdr, previous_fdr)):
-                if had:
-                    data.obs[key] = prev
-                elif key in data.obs:
-                    del data.obs[key]
+    # nothing written by this call outlives an exception or a detour through the general path
+    snap = _result.ObsSnapshot(data.obs, key_added, fdr_key)
 
     def give_up(kind, stale=False):
-        roll_back()
+        snap.restore()
         native.abandon()                       # numpy's generator stays as it was found
         if stale:                              # some input is no longer what went to the device: both memos go
             _nam_mod.drop_codes_memo()
@@ -308,7 +277,7 @@ def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_f
             if plan.kind != 'single' or plan.r != r or not _lowrank_ok(engine, plan) or not np.isfinite(Mv).all():
                 return give_up('general')      # (a constant covariate: the general path raises the reference's error)
         _mark('plan')
-        touched[0] = True
+        snap.written = True
         data.obs[key_added] = np.empty(n)
         data.obs[fdr_key] = np.empty(n)
         coef_view, fdr_view = data.obs[key_added].values, data.obs[fdr_key].values
@@ -344,25 +313,13 @@ def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_f
             eig_stats['native'] += 1
             pcs = None
             Uk, best, pv, r2v = out['U'], out['kidx'], out['minp'], out['r2']
-        if (best < 0).any():
-            raise ValueError('All-NaN slice encountered')        # np.nanargmin in _minp_stats
-        k, p = ks_[best[0]], pv[0]
-        if k == max(ks_):
-            warnings.warn(('data supported use of {} NAM PCs, which is the maximum considered. ' +
-                           'Consider allowing more PCs by using the "ks" argument.').format(k))
-        nullminps = pv[1:]
-        hits = (nullminps <= p + 1e-8).sum()
-        pfinal = (hits + 1) / (Nnull + 1)
-        if hits == 0:
-            warnings.warn('global association p-value attained minimal possible value. ' +
-                          'Consider increasing Nnull')
+        found = _result.verdict(best, pv, r2v, ks_, Nnull)
         fdr_vals = out['fdr']
         if return_full or np.isnan(fdr_vals).all():
-            # (a table without a single finite entry: the reference fails in its np.min -- and so does _fdr_tables)
-            from ._association import _fdr_tables
-            fdr_vals, fdr_5p_t, fdr_10p_t, _ = _fdr_tables(out['tail_sums'], out['ranks'], min(1000, Nnull), out['thr'].copy())
+            # (a table without a single finite entry: the reference fails in its np.min -- and so does fdr_tables)
+            fdr_vals, fdr_5p_t, fdr_10p_t, _ = fdr_tables(out['tail_sums'], out['ranks'], min(1000, Nnull), out['thr'].copy())
         _mark('p')
-        if had_key:
+        if snap.had(key_added):
             warnings.warn(f"Key '{key_added}' already exists in data.obs. Overwriting.")
         # data.obs[key], data.obs[key + '_fdr'] (_association.py:230-237): filled in place by the library, unless the
         # frame's storage could not be written that way
@@ -370,13 +327,13 @@ def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_f
             data.obs[key_added] = np.array(out['coef'])
         if not (out['fdr_in_dst'] and np.shares_memory(data.obs[fdr_key].values, fdr_view)):
             data.obs[fdr_key] = np.array(out['fdr_col'])
-        touched[0] = False
+        snap.written = False
         _mark('obs checked')
         if return_full:
-            res = _full_result(engine, data, out, pcs, Uk, best, pv, r2v, k, pfinal, ks, ks_, r, N, n, Mv, M_frame, y_std,
+            res = _full_result(engine, data, out, pcs, Uk, found, ks, ks_, r, N, n, Mv, M_frame, y_std,
                                sample_index, colmap, key_added, max_frac_pcs, nam_epoch, fdr_vals, fdr_5p_t, fdr_10p_t)
     except BaseException:
-        roll_back()
+        snap.restore()
         native.abandon()
         for undo in (engine.null_local_discard, engine.global_test_discard):
             try:
@@ -387,35 +344,22 @@ def association(data, y, sid_name, batches, covs, donorids, ks, key_added, max_f
     finally:
         engine._defer_graph_check = False
     stats['taken'] += 1
-    return res if return_full else pfinal
+    return res if return_full else found[3]           # (pfinal)
 
 
 def _verify_threads(verify):
     """Threads of the content check inside cna_assoc_finish: one for an id column of a few MB, the host's share for a graph."""
-    global _cpus
     if not verify or sum(a.nbytes for a, _ in verify) < (8 << 20):
         return 1
-    if _cpus is None:
-        from .._order import usable_cpus
-        _cpus = usable_cpus(8)
-    return min(4, _cpus)                       # (beside the draw's threads and the eigenpairs: see tools/_stats.py)
+    return usable_cpus(4)                      # (beside the draw's threads and the eigenpairs: see tools/_stats.py)
 
 
-def _full_result(engine, data, out, pcs, Uk, best, pv, r2v, k, pfinal, ks, ks_, r, N, n, Mv, M_frame, y_std, sample_index,
-                 colmap, key_added, max_frac_pcs, nam_epoch, fdr_vals, fdr_5p_t, fdr_10p_t):
+def _full_result(engine, data, out, pcs, Uk, found, ks, ks_, r, N, n, Mv, M_frame, y_std, sample_index, colmap, key_added,
+                 max_frac_pcs, nam_epoch, fdr_vals, fdr_5p_t, fdr_10p_t):
     """The result namespace (_association.py:64-129, _nam.py:168-175): cells-sized and sign-defining fields
     on demand, everything else materialised like upstream."""
     if pcs is None:
         pcs = GramPCs(out['G'])
-    r2 = r2v[0]
-    nullminps, nullr2s = pv[1:], r2v[1:]
-    # coefficients and r2 of the chosen model (_association.py:69-74)
-    ycond_v = Mv.dot(y_std)
-    ycond_v = ycond_v / ycond_v.std(ddof=1)
-    beta_k = Uk[:, :k].T.dot(ycond_v)
-    yhat = Uk[:, :k].dot(beta_k)
-    r2_perpc = (beta_k / np.sqrt(ycond_v.dot(ycond_v))) ** 2
-    thresholds, num_detected = out['thr'].copy(), out['num_detected'].copy()     # (views of the library call's output block)
     res = LazyNamespace()
     res.M = M_frame if M_frame is not None else pd.DataFrame(np.eye(N), columns=sample_index, index=sample_index)
     res.r = r
@@ -428,33 +372,11 @@ def _full_result(engine, data, out, pcs, Uk, best, pv, r2v, k, pfinal, ks, ks_, 
         _still_resident(engine, x_epoch)
         return pd.DataFrame(engine.x_full(transposed=True), index=sample_index, columns=cell_index())
     res._defer('namresid', fetch_namresid)
-
-    def names():
-        return ['PC' + str(i) for i in range(1, N + 1)]
-    npcs = min(N, max([10] + [int(max_frac_pcs * N)] + [ks if ks is not None else []][0]))
-    res._defer('namresid_sampleXpc', lambda: pd.DataFrame(pcs.U, index=sample_index, columns=names()))
-    res._defer('namresid_svs', lambda: pd.Series(pcs.svs, index=names())[:npcs])
-    res._defer('namresid_varexp', lambda: pd.Series(pcs.svs, index=names()) / N / engine.x_rows_global())   # (all ranks' cells)
-    res._defer('yresid', lambda: pd.Series(ycond_v, index=sample_index))
-    res._defer('beta', lambda: pcs.U[:, :k].T.dot(ycond_v))
-    res._defer('fdrs', lambda: pd.DataFrame({'threshold': thresholds, 'fdr': fdr_vals, 'num_detected': num_detected}))
-    res.__dict__.update({'p': pfinal, 'nullminps': nullminps, 'k': k, 'fdr_5p_t': fdr_5p_t, 'fdr_10p_t': fdr_10p_t,
-                         'yresid_hat': yhat, 'ks': ks_, 'r2': r2, 'r2_perpc': r2_perpc, 'nullr2_mean': nullr2s.mean(),
-                         'nullr2_std': nullr2s.std()})
-    _defer_pcs(res, engine, pcs, cell_index)
-    kept = np.repeat(True, n)
-    res.kept = kept
-
-    def fetch_nam():
-        if engine.nam_epoch != nam_epoch:
-            raise RuntimeError('res.nam lives on the GPU and a later cna_amd call has replaced it; '
-                               'read it (or call res.materialize()) before running the next analysis')
-        return pd.DataFrame(engine.nam_full(keep=kept, cols=colmap, transposed=True), index=sample_index,
-                            columns=cell_index(), copy=False)
-    res._defer('nam', fetch_nam)
-    coef_kept = data.obs[key_added].values
-    res._defer('ncorrs', lambda: pd.Series(coef_kept, index=cell_index()))
-    # everything but the three cells x samples frames is materialised now, like upstream
-    for name in ('ncorrs', 'fdrs', 'namresid_sampleXpc', 'namresid_svs', 'namresid_varexp', 'yresid', 'beta'):
+    # (thresholds and counts: views of the library call's output block)
+    _result.sample_fields(res, pcs, Uk, Mv, y_std, sample_index, ks_, _result.kept_pcs(N, max_frac_pcs, ks), engine.x_rows_global,
+                          found, (out['thr'].copy(), fdr_vals, out['num_detected'].copy()), fdr_5p_t, fdr_10p_t)
+    _result.cell_fields(res, engine, pcs, np.repeat(True, n), colmap, sample_index, cell_index, nam_epoch,
+                        data.obs[key_added].values)
+    for name in _result.FULL_FIELDS:
         getattr(res, name)
     return res

@@ -342,3 +342,81 @@ def test_helper_threads_take_their_ranks_share_of_the_cpu_allowance(monkeypatch)
     assert _order.ranks_on_this_node() == 4 and _order.usable_cpus() == max(1, alone // 4)
     monkeypatch.setenv('LOCAL_WORLD_SIZE', 'garbage')
     assert _order.ranks_on_this_node() == 4
+
+
+def test_verdict_values_errors_and_warning_order():
+    """_result.verdict, which both call paths use (_association.py:55-62, :84-88): np.nanargmin's error for an all-NaN
+    slice, the two warnings in the reference's order, values equal to the reference's arithmetic restated here."""
+    import warnings
+    from cna_amd.tools._result import verdict
+    ks, Nnull = [2, 4, 6], 10
+    rs = np.random.RandomState(1)
+    pv = np.concatenate([[0.2], rs.uniform(0.05, 1, Nnull)])
+    pv[3] = 0.2 + 5e-9                                    # within the 1e-8 of the comparison: counts as a hit
+    r2v = rs.uniform(0, 1, Nnull + 1)
+
+    def run(best0, pv_):
+        best = np.array([best0] + [0] * Nnull)
+        with warnings.catch_warnings(record=True) as rec:
+            warnings.simplefilter('always')
+            got = verdict(best, pv_, r2v, ks, Nnull)
+        return got, [str(w.message) for w in rec]
+
+    (k, p, r2, pfinal, nullminps, nullr2s), msgs = run(1, pv)
+    hits = (pv[1:] <= pv[0] + 1e-8).sum()
+    assert hits >= 1 and msgs == []
+    assert (k, p, r2) == (4, pv[0], r2v[0]) and pfinal == (hits + 1) / (Nnull + 1)
+    np.testing.assert_array_equal(nullminps, pv[1:])
+    np.testing.assert_array_equal(nullr2s, r2v[1:])
+
+    _, msgs = run(2, pv)                                   # k == max(ks)
+    assert len(msgs) == 1 and msgs[0].startswith('data supported use of 6 NAM PCs, which is the maximum considered.')
+
+    low = pv.copy()
+    low[0] = 0.001                                         # no permutation as small: the smallest p-value there is
+    (k, p, _, pfinal, _, _), msgs = run(0, low)
+    assert k == 2 and p == 0.001 and pfinal == 1 / (Nnull + 1)
+    assert len(msgs) == 1 and msgs[0].startswith('global association p-value attained minimal possible value.')
+
+    _, msgs = run(2, low)                                  # both, in the reference's order
+    assert [m.split(' ')[0] for m in msgs] == ['data', 'global'] and 'Consider increasing Nnull' in msgs[1]
+
+    bad = np.array([1] + [0] * Nnull)
+    bad[4] = -1
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter('always')
+        with pytest.raises(ValueError, match='All-NaN slice encountered'):
+            verdict(bad, low, r2v, [2, 4], Nnull)         # (k would be max(ks): the error comes before any warning)
+    assert not rec
+
+
+def test_obs_snapshot_puts_columns_back_once():
+    """_result.ObsSnapshot: what both call paths use to leave data.obs alone after an error."""
+    from cna_amd.tools._result import ObsSnapshot
+    obs = pd.DataFrame({'coef': np.arange(5.0), 'other': np.ones(5)})
+    before = obs['coef'].values.copy()
+    snap = ObsSnapshot(obs, 'coef', 'coef_fdr')
+    assert snap.had('coef') and not snap.had('coef_fdr')
+    snap.restore()                                         # nothing written yet: nothing to do
+    assert list(obs.columns) == ['coef', 'other']
+    snap.written = True
+    obs['coef'] = np.full(5, 7.0)
+    obs['coef_fdr'] = np.zeros(5)
+    snap.restore()
+    np.testing.assert_array_equal(obs['coef'].values, before)
+    np.testing.assert_array_equal(obs['other'].values, np.ones(5))
+    assert 'coef_fdr' not in obs and list(obs.columns) == ['coef', 'other'] and not snap.written
+    obs['coef'] = np.full(5, 9.0)                          # a later, successful write is not undone by a second restore
+    obs['coef_fdr'] = np.zeros(5)
+    snap.restore()
+    np.testing.assert_array_equal(obs['coef'].values, np.full(5, 9.0))
+    assert 'coef_fdr' in obs
+    # one column by itself (the general path decides per column)
+    snap2 = ObsSnapshot(obs, 'coef', 'coef_fdr')
+    obs['coef_fdr'] = np.ones(5)
+    del obs['coef']
+    snap2.put_back('coef')
+    np.testing.assert_array_equal(obs['coef'].values, np.full(5, 9.0))
+    np.testing.assert_array_equal(obs['coef_fdr'].values, np.ones(5))
+    snap2.put_back('coef_fdr')
+    np.testing.assert_array_equal(obs['coef_fdr'].values, np.zeros(5))
