@@ -181,7 +181,7 @@ int cna_assoc_finish(cna_ctx* c, const cna_assoc_args* a, cna_assoc_out* o) {
       }
     }
     mark(4);
-    // the FDR column follows the local null on the device (c_api.hip:null_local_go, fdr_inline): put together in the
+    // the FDR column follows the local null on the device (local_null.hip:null_local_go, fdr_inline): put together in the
     // caller's storage the moment the pass is done
     int fdr_done = 0;
     if (to_dst && cq) CNA_TRY(cna_percell_fdr_copy_early(c, a->fdr_dst, n_out, threads, &fdr_done));

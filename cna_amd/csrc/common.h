@@ -53,7 +53,51 @@ struct GramPlan {
   size_t smem = 0;
 };
 
-// Derived state: each flag below that says "still holds" is tagged with the transition of c_api.hip that clears it --
+// ---- the local-null pass and the per-cell columns that ride on it (local_null.hip)
+// c->scratch of one pass (null_carve): every piece is there from the prepare half to the fetch (NO_NULL_PENDING)
+struct NullCarve {
+  double *cuts, *obs_edges, *obs_thr;      // T each (obs_*: the threshold counts of the observed coefficients, passes with thresholds)
+  unsigned long long *hist, *obs_hist;     // P x T, 2 x T
+  int64_t *tails, *sums, *obs_tails;       // P x T, T, [ranks | num_detected]
+};
+// byte offsets into the pinned block c->h_res of one pass (null_host_layout): [T sums][P x T tails if requested]
+// [2T observed counts][staging: cuts | edges | thr, so that the uploads need no wait][the integer pass's status word]
+struct NullHostLayout { int64_t sums = 0, tails = 0, obs = 0, stage = 0, status = 0, bytes = 0; };
+enum NullPhase : int { NULL_IDLE = 0, NULL_PREPARED, NULL_PENDING };   // prepare -> go -> collect (or discard)
+// One pass.  A helper thread inside cna_percell_fdr_copy_early reads the atomics of both structs while the main thread
+// collects the pass.  The rule: when the integer pass gave up (status word raised), null_local_collect clears fdr_inline
+// FIRST, reruns in f64, and resets status_off only AFTERWARDS -- so the helper, which reads the word through status_off
+// and then fdr_inline, sees the raised word or fdr_inline == false, never the void FDR table as a valid one.  The
+// helper also reads T, a plain int: it is written only in prepare, before the phase it has seen became NULL_PENDING.
+struct NullPass {
+  int P = 0, T = 0, col0 = 0, has_tails = 0, has_obs = 0;   // col0: first column of Zc
+  double cut0 = 0, inv_step = 0, eps = 0;    // the line the exact cuts lie near (exact_cuts)
+  double thr0 = 0, thr_step = 0;             // linear guess over the thresholds
+  bool i8_last = false;                      // the last pass took the integer path
+  NullHostLayout host;
+  std::atomic<int> phase{NULL_IDLE};
+  std::atomic<int64_t> status_off{-1};       // >= 0: h_res + off holds the pending integer pass's status word (0: its sums stand)
+};
+struct CellColumns {
+  std::atomic<bool> coef_early{false};        // [void_x] h_cell[0, n_out) already holds the coefficients of the current ncorrs
+  std::atomic<bool> fdr_inline{false};        // [void_x] ... and the FDR column follows the last local-null pass on the device
+  std::atomic<bool> fdr_early_copied{false};  // cna_percell_fdr_copy_early took the FDR column of the pending pass ...
+  std::atomic<bool> fdr_early_served{false};  // ... and cna_percell_fdr_pinned then returned that same column
+  std::atomic<int> fdr_early_inflight{0};     // a helper thread is inside cna_percell_fdr_copy_early
+  double* fdr_early_dst = nullptr;            // where it put the column
+  double* coef_dev = nullptr;                 // early copy of the coefficients (cna_percell_coef_launch): coef, coef_u, fdr, fdr_u, FDR table
+  // fdr_inline: the per-cell threshold counts (16 bits, caller's order) cross PCIe while the null runs, the FDR table
+  // follows it, and the host puts the two together (cna_percell_fdr_copy_early / cna_percell_fdr_pinned)
+  unsigned short* bins_dev = nullptr;
+  unsigned short* h_bins = nullptr;           // pinned
+  bool bins_pending = false;                  // the copy on coef_stream may still read the thresholds in c->scratch
+  double* h_tab = nullptr;                    // pinned: running minimum of the FDR table (512 doubles)
+  void* h_cell = nullptr;                     // pinned: per-cell outputs of cna_percell_fdr_pinned (coef | fdr)
+  int64_t coef_dev_cap = 0, bins_cap = 0, h_bins_cap = 0, h_cell_cap = 0;
+  hipEvent_t coef_ready = nullptr, coef_copied = nullptr, bins_copied = nullptr;
+};
+
+// Derived state: each flag (here and in CellColumns) that says "still holds" is tagged with the transition of c_api.hip that clears it --
 // [void_x] X and what is derived from it, [void_walk] the walk and then X, [void_cells] the cell space and then the walk.
 // A new such flag goes into the transition of what it is derived from.
 struct cna_ctx {
@@ -75,13 +119,8 @@ struct cna_ctx {
                                        // variable -- is staged by the runtime: 20-25 us each, measured between the selection pass and the Gram kernel)
   void* h_res = nullptr;               // pinned host staging for asynchronously fetched results
   int64_t h_res_cap = 0;
-  int null_P = 0, null_T = 0, null_has_tails = 0;
-  int null_col0 = 0;                   // first column of Zc of the pending pass
-  // >= 0: h_res + off holds the integer pass's status word of the pending pass (0: its sums stand); read by the helper
-  // thread's cna_percell_fdr_copy_early, reset only once a rerun is over (null_local_collect)
-  std::atomic<int64_t> null_status_off{-1};
-  int64_t null_stage_off = 0;          // h_res + off: the pinned copy of the prepared pass's exact cuts (its f64 rerun uploads them)
-  std::atomic<int> null_pending{0};   // (read by the helper thread's cna_percell_fdr_copy_early, like the four flags below)
+  NullPass null;                       // the local-null pass between prepare and fetch
+  CellColumns cells;                   // the per-cell columns that ride on it
   int64_t gram_cap = 0;
   int gram_n = 0;                      // [void_x] order of the Gram matrix in h_gram (0: none)
   std::atomic<int64_t> dev_bytes{0};   // (two host threads may reserve buffers of one context at once: the F-tests from the eigenvector thread)
@@ -223,38 +262,12 @@ struct cna_ctx {
   int64_t proj_cap = 0, proj_rows = 0;
   int proj_ld = 0, proj_cols = 0;
   bool proj_valid = false;        // [void_x]
-  int null_prepared = 0;          // cna_null_local_prepare done, launch still to come
-  double null_cut0 = 0, null_inv_step = 0, null_eps = 0;
-  int null_has_obs = 0;
-  int64_t null_obs_off = 0;
   void* h_gt = nullptr;           // pinned staging of cna_global_test_launch / _fetch: U, ks | minp, r2, kidx
   int64_t h_gt_cap = 0;
   hipEvent_t gt_done = nullptr;
   hipEvent_t stage_done = nullptr;   // uploads out of h_res' staging tail (cna_null_local_prepare) have been issued and finished
   int gt_pending_P = 0;           // > 0: a launched global test waits to be fetched (its number of columns)
   int64_t gt_off_out = 0;
-  double* coef_dev = nullptr;     // early copy of the per-cell coefficients (cna_percell_coef_launch): 2 x n_pad
-  int64_t coef_dev_cap = 0;
-  hipEvent_t coef_ready = nullptr, coef_copied = nullptr;
-  std::atomic<bool> coef_early{false};        // [void_x] h_cell[0, n_out) already holds the coefficients of the current ncorrs
-  std::atomic<bool> fdr_inline{false};        // [void_x] ... and h_cell[n_out, 2 n_out) the per-cell FDRs of the last local-null pass
-  double null_thr0 = 0, null_thr_step = 0;   // linear guess over the thresholds of the prepared pass
-  std::atomic<bool> fdr_early_copied{false};  // cna_percell_fdr_copy_early took the FDR column of the pending pass ...
-  std::atomic<bool> fdr_early_served{false};  // ... and cna_percell_fdr_pinned then returned that same column
-  // the FDR column behind a local-null pass that was launched with the coefficient column already out (fdr_inline):
-  // the per-cell threshold counts (16 bits, caller's order) cross PCIe while the null runs, the FDR table follows it,
-  // and the host puts the two together (cna_percell_fdr_copy_early / cna_percell_fdr_pinned)
-  unsigned short* bins_dev = nullptr;
-  int64_t bins_cap = 0;
-  unsigned short* h_bins = nullptr;   // pinned
-  int64_t h_bins_cap = 0;
-  double* h_tab = nullptr;            // pinned: running minimum of the FDR table (512 doubles)
-  hipEvent_t bins_copied = nullptr;
-  bool bins_pending = false;          // the copy on coef_stream may still read the thresholds in c->scratch
-  double* fdr_early_dst = nullptr;    // where cna_percell_fdr_copy_early put the column
-  std::atomic<int> fdr_early_inflight{0};   // a helper thread is inside cna_percell_fdr_copy_early
-  void* h_cell = nullptr;         // pinned: per-cell outputs of cna_percell_fdr_pinned (coef | fdr)
-  int64_t h_cell_cap = 0;
   // compressed copy of the state after the first walk step (single GPU, wide sample axis)
   void* sp_pair = nullptr;
   void* sp_cnt = nullptr;
@@ -268,7 +281,6 @@ struct cna_ctx {
   bool xq_valid = false;          // [void_x] they describe the current X
   int64_t xq_rows = 0;
   int xq_KS = 0;
-  bool i8_last = false;           // the last local-null pass took the integer path
   unsigned long long* i8_qcount = nullptr;   // device: [0] outputs sent to the f64 recheck by the last pass, [1] low word = status
   void* null_part = nullptr;      // per-block counter slabs of the local-null kernel
   int64_t null_part_cap = 0;
@@ -324,6 +336,46 @@ int dev_alloc(cna_ctx* c, void** p, size_t bytes);
 int dev_free(cna_ctx* c, void* p, size_t bytes);
 // grow-only buffer: (re)allocates *p when cap < need (contents discarded)
 int dev_reserve(cna_ctx* c, void** p, int64_t* cap_bytes, int64_t need_bytes);
+
+#define CHECK_CTX(c)                                        \
+  do {                                                      \
+    if (!(c)) CNA_FAIL(CNA_EINVAL, "null context");         \
+    HIP_TRY(hipSetDevice((c)->device));                     \
+  } while (0)
+
+// The contract of a pending local-null pass (launched, not yet fetched): should its integer kernel give up, the fetch
+// reruns it in f64 on the X and Zc the launch saw (null_local_collect).  So every entry point that rewrites X or carves
+// c->scratch refuses with CNA_ESTATE until the pass is fetched (or discarded); nothing is queued and no state changes.
+// Entry points on other buffers (Gram, F-tests, the coefficient column, the FDR copy) may run in between.  Every writer
+// of X checks in x_begin; the selections that queue work before it (materialising the NAM) check at their top as well.
+#define NO_NULL_PENDING(c, who)                                                                      \
+  do {                                                                                               \
+    if ((c)->null.phase == NULL_PENDING)                                                             \
+      CNA_FAIL(CNA_ESTATE, std::string(who) + ": a local-null pass is still pending: fetch it first"); \
+  } while (0)
+
+// scratch layout helper: carve 256-byte aligned pieces out of a buffer
+struct Carver {
+  char* base;
+  int64_t off = 0;
+  explicit Carver(void* p) : base((char*)p) {}
+  template <typename T>
+  T* take(int64_t count) {
+    T* r = (T*)(base + off);
+    off += round_up64((int64_t)sizeof(T) * count, 256);
+    return r;
+  }
+};
+inline int64_t carve_bytes(std::initializer_list<int64_t> sizes) {
+  int64_t t = 0;
+  for (auto s : sizes) t += round_up64(s, 256);
+  return t;
+}
+
+int x_ld(int Nx);   // c_api.hip: leading dimension of a working matrix with Nx samples
+// local_null.hip: the two halves of a pass (cna_select_standardized_fused issues them itself)
+int null_local_prepare(cna_ctx* c, int P, const double* edges, int T, int want_tails, const double* thr);
+int null_local_go(cna_ctx* c, int col0);
 
 // genes.hip: frees the resident expression matrix and its state (cna_ctx_destroy)
 void expr_destroy(cna_ctx* c);

@@ -680,22 +680,16 @@ void expr_destroy(cna_ctx* c) {
   c->expr = nullptr;
 }
 
-#define GC_CHECK_CTX(c)                                      \
-  do {                                                       \
-    if (!(c)) CNA_FAIL(CNA_EINVAL, "null context");          \
-    HIP_TRY(hipSetDevice((c)->device));                      \
-  } while (0)
-
 extern "C" {
 
 int cna_expr_drop(cna_ctx* c) {
-  GC_CHECK_CTX(c);
+  CHECK_CTX(c);
   if (state_of(c)) release_matrix(c, state_of(c));
   return 0;
 }
 
 int cna_expr_shape(cna_ctx* c, int64_t* n_cells, int64_t* n_genes, int64_t* nnz, int* format, int* is_f64, int64_t* n_uploads) {
-  GC_CHECK_CTX(c);
+  CHECK_CTX(c);
   const ExprState* s = state_of(c);
   if (n_cells) *n_cells = s ? s->n : 0;
   if (n_genes) *n_genes = s ? s->G : 0;
@@ -707,7 +701,7 @@ int cna_expr_shape(cna_ctx* c, int64_t* n_cells, int64_t* n_genes, int64_t* nnz,
 }
 
 int cna_expr_upload_dense(cna_ctx* c, const void* x, int64_t n_cells, int64_t n_genes, int is_f64) {
-  GC_CHECK_CTX(c);
+  CHECK_CTX(c);
   if (!x) CNA_FAIL(CNA_EINVAL, "expression matrix: null pointer");
   if (n_cells < 1 || n_genes < 1 || n_cells >= (1ll << 31) || n_genes >= (1ll << 31))
     CNA_FAIL(CNA_EINVAL, "expression matrix: cells and genes must lie in [1, 2^31)");
@@ -738,7 +732,7 @@ int cna_expr_upload_dense(cna_ctx* c, const void* x, int64_t n_cells, int64_t n_
 
 int cna_expr_upload_sparse(cna_ctx* c, const void* indptr, const void* indices, const void* data, int64_t n_cells,
                            int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc) {
-  GC_CHECK_CTX(c);
+  CHECK_CTX(c);
   if (!indptr || (nnz > 0 && (!indices || !data))) CNA_FAIL(CNA_EINVAL, "expression matrix: null pointer");
   if (n_cells < 1 || n_genes < 1 || n_cells >= (1ll << 31) || n_genes >= (1ll << 31) || nnz < 0)
     CNA_FAIL(CNA_EINVAL, "expression matrix: cells and genes must lie in [1, 2^31), nnz in [0, 2^63)");
@@ -761,7 +755,7 @@ int cna_expr_upload_sparse(cna_ctx* c, const void* indptr, const void* indices, 
 }
 
 int cna_gene_corr(cna_ctx* c, const double* V, int q, double* r_out) {
-  GC_CHECK_CTX(c);
+  CHECK_CTX(c);
   ExprState* s = state_of(c);
   if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_gene_corr: no expression matrix is resident (cna_expr_upload_*)");
   if (!V || !r_out) CNA_FAIL(CNA_EINVAL, "cna_gene_corr: null pointer");

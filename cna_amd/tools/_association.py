@@ -634,7 +634,7 @@ def compute_nam_and_reindex(engine, data, y, sid_name, batches, covs, donorids, 
 
 def _drop_pending_null(engine):
     """On an error path: the local-null pass the fused selection call may have launched is dropped, else the library
-    refuses the next call's entry points that would disturb it (c_api.hip: NO_NULL_PENDING)."""
+    refuses the next call's entry points that would disturb it (csrc/common.h: NO_NULL_PENDING)."""
     if getattr(engine, 'null_local_discard', None) is not None:
         try:
             engine.null_local_discard()

@@ -2,7 +2,7 @@
 
 A local-null pass lives from cna_null_local_launch to cna_null_local_fetch.  Should its integer kernel give up (a recheck
 queue overflow, forced here through CNA_I8_QCAP), the fetch reruns it on the f64 kernel -- on the X, the conditioned
-phenotypes and the exact cuts the launch saw.  The contract (csrc/c_api.hip: NO_NULL_PENDING): an entry point that would
+phenotypes and the exact cuts the launch saw.  The contract (csrc/common.h: NO_NULL_PENDING): an entry point that would
 rewrite X or carve the scratch those cuts live in refuses with CNA_ESTATE while a pass is pending, changes nothing, and
 the fetch returns the f64 kernel's integers.  Also here: the FDR column the helper thread copies while a given-up pass is
 collected, and the Gram matrix queued with a selection that turns out to have cells of zero variance.
@@ -219,6 +219,25 @@ def test_helper_thread_fdr_copy_while_the_main_thread_fetches(eng, resident, ref
         assert (dst == -1.0).all()
     if give_up:
         assert not eng.percell_fdr_copied_early()
+
+
+def test_pass_with_thresholds_and_tails(eng, resident):
+    """cna_null_local_launch with thresholds AND want_tails (no Engine method asks for both): the observed counts then
+    sit behind the P x T tails in the pinned result block.  One fetch with all four outputs returns the f64 kernel's
+    tails, their column sums and the observed counts of cna_obs_counts, integer for integer."""
+    from cna_amd._ffi import check, ptr
+    codes, thr, edges = resident['setup'](eng)
+    T = len(edges)
+    want_tails = eng.null_local_resident(1, P, edges)
+    want_ranks, want_numdet = eng.obs_counts(edges, thr)
+    check(eng.lib.cna_null_local_launch(eng.h, 1, P, ptr(edges), T, 1, ptr(thr)), 'cna_null_local_launch')
+    tails = np.full((P, T), -1, dtype=np.int64)
+    sums, ranks, numdet = (np.full(T, -1, dtype=np.int64) for _ in range(3))
+    check(eng.lib.cna_null_local_fetch(eng.h, ptr(tails), ptr(sums), ptr(ranks), ptr(numdet)), 'cna_null_local_fetch')
+    np.testing.assert_array_equal(tails, want_tails)
+    np.testing.assert_array_equal(sums, want_tails.sum(axis=0))
+    np.testing.assert_array_equal(ranks, want_ranks)
+    np.testing.assert_array_equal(numdet, want_numdet)
 
 
 def _with_zero_variance_cells(n_samples, seed):
