@@ -139,6 +139,7 @@ SIGNATURES = {
     'cna_expr_drop': (C.c_int, [c_ctx]),
     'cna_expr_shape': (C.c_int, [c_ctx, c_i64p, c_i64p, c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_i64p]),
     'cna_gene_corr': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p]),
+    'cna_expr_to_bins': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 MAT_NAM, MAT_X, MAT_PROJ = 0, 1, 2

@@ -15,6 +15,23 @@
 //   k_gc_finish_*   adds the partials of a gene in slab / chunk order and turns them into r
 //   k_tr_*          counting transpose of a CSR upload into the gene-major form, stable in the cell index
 //
+// Per-bin sums of the same resident matrix (cna.ut.expr_to_sample: the samples x genes "pseudobulk" that stands beside
+// the reference's utils/multisample.py:4-11 obs_to_sample), cna_expr_to_bins:
+//   k_pb_count      checks every code against [-1, n_bins) and counts the cells of every bin per block of cells
+//                   (integer atomics in LDS); k_tr_scan turns the counts into offsets
+//   k_pb_fill       the cells sorted by bin, ascending inside a bin whatever the scheduling: a wave takes 64 cells at a
+//                   time in order and ranks equal codes by lane (dense form only: the lists carry their cell already)
+//   k_pb_dense      lane = gene, a workgroup walks a chunk (PB_DENSE_CHUNK cells) of one bin's cell list, every row read
+//                   a coalesced run of genes; one partial per (chunk, gene) with plain stores
+//   k_pb_sparse     one wave per chunk of a gene's list, the bins' accumulators in LDS (4096 doubles at most); lanes of
+//                   one batch that meet in a bin are served lowest lane first, in rounds (an integer LDS atomic names
+//                   the lane whose turn it is); one partial per (chunk, bin) with plain stores
+//   k_pb_finish_*   adds the partials of a (bin, gene) in chunk order
+// Partial storage: dense (cells / PB_DENSE_CHUNK + min(cells, n_bins)) x genes doubles -- never more than the result plus
+// 1 / 1024 of the matrix' own size (f32); gene-major lists: chunks x n_bins doubles, held to PB_PART_BYTES (256 MB) by
+// going over the genes in tiles (a single gene whose chunks alone exceed it gets a tile of its own: at most 2^31 / 65536
+// chunks x 4096 bins x 8 bytes = 1 GB).
+//
 // Result sums take a fixed order (no floating-point atomics): two runs on one input give the same bits.  Integer
 // atomics only count and hand out cursors.
 #include "common.h"
@@ -46,6 +63,9 @@ struct ExprState {
   int64_t nchunks = 0, chunk_len = 0;
   // per call (grow-only until the matrix is dropped)
   Buf vraw, vtab, vmask, kstat, part, rout, flag;
+  // cna_expr_to_bins: codes, per-block counts -> offsets, totals, the cell list, the chunks of the bins
+  Buf bcode, bcnt, btot, blist, bptr, brng, bfirst;
+  std::vector<int64_t> gchunk_h;   // host copy of gchunk (tiles over genes)
 };
 
 inline ExprState* state_of(cna_ctx* c) { return static_cast<ExprState*>(c->expr); }
@@ -72,8 +92,10 @@ int buf_need(cna_ctx* c, ExprState* s, Buf& b, int64_t bytes) {
 void release_matrix(cna_ctx* c, ExprState* s) {
   (void)hipStreamSynchronize(s->st);
   for (Buf* b : {&s->X, &s->gptr, &s->gcell, &s->gval, &s->chunk_lo, &s->chunk_gene, &s->gchunk, &s->vraw, &s->vtab,
-                 &s->vmask, &s->kstat, &s->part, &s->rout, &s->flag})
+                 &s->vmask, &s->kstat, &s->part, &s->rout, &s->flag, &s->bcode, &s->bcnt, &s->btot, &s->blist, &s->bptr, &s->brng,
+                 &s->bfirst})
     buf_free(c, *b);
+  s->gchunk_h.clear();
   s->format = 0;
   s->n = s->G = s->nnz = 0;
   s->nchunks = s->chunk_len = 0;
@@ -491,6 +513,7 @@ int build_chunks(cna_ctx* c, ExprState* s, const std::vector<int64_t>& gptr) {
     }
   }
   first[(size_t)s->G] = (int64_t)lo.size();
+  s->gchunk_h = first;
   s->nchunks = (int64_t)lo.size();
   s->chunk_len = len;
   CNA_TRY(buf_need(c, s, s->chunk_lo, 8 * std::max<int64_t>(1, s->nchunks)));
@@ -669,6 +692,254 @@ int launch_pass(ExprState* s, int Q, bool shared, int nslab, int64_t slab_rows) 
   }
 }
 
+// ------------------------------------------------------------------ per-bin sums (cna_expr_to_bins)
+constexpr int PB_MAX_BINS = 4096;
+constexpr int64_t PB_DENSE_CHUNK = 2048;          // cells of one bin that one workgroup of k_pb_dense adds up
+constexpr int64_t PB_PART_BYTES = 256ll << 20;    // partial sums of the gene-major kernel kept at a time
+constexpr int PB_MAX_BLOCKS = 1024;               // blocks of cells of the counting sort
+
+// block b: cnt[b][bin] = cells of [r0, r1) with that code; *bad |= 1 for a code outside [-1, n_bins)
+__global__ __launch_bounds__(256) void k_pb_count(const int32_t* __restrict__ codes, int64_t n, int n_bins, int64_t rows_per_block,
+                                                  unsigned int* __restrict__ cnt, int* __restrict__ bad) {
+  __shared__ unsigned int h[PB_MAX_BINS];
+  for (int b = threadIdx.x; b < n_bins; b += blockDim.x) h[b] = 0;
+  __syncthreads();
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += blockDim.x) {
+    const int32_t cd = codes[i];
+    if (cd < -1 || cd >= n_bins) atomicOr(bad, 1);
+    else if (cd >= 0) atomicAdd(&h[cd], 1u);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < n_bins; b += blockDim.x) cnt[(int64_t)blockIdx.x * n_bins + b] = h[b];
+}
+
+// one wave per block of cells; cur[bin] = cells of the bin in the blocks before this one plus those already placed.  Among
+// the 64 cells of a batch equal codes are ranked by lane, so a bin's cells ascend.
+__global__ __launch_bounds__(64) void k_pb_fill(const int32_t* __restrict__ codes, int64_t n, int n_bins, int64_t rows_per_block,
+                                                const unsigned int* __restrict__ cnt, const int64_t* __restrict__ bptr,
+                                                int32_t* __restrict__ list) {
+  __shared__ unsigned int cur[PB_MAX_BINS];
+  const int lane = threadIdx.x;
+  for (int b = lane; b < n_bins; b += 64) cur[b] = cnt[(int64_t)blockIdx.x * n_bins + b];
+  __syncthreads();
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+  for (int64_t base = r0; base < r1; base += 64) {
+    const int64_t i = base + lane;
+    const int32_t cd = i < r1 ? codes[i] : -1;
+    unsigned int rank = 0;
+    bool last = true;
+    for (int j = 0; j < 64; ++j) {
+      const bool same = __shfl(cd, j, 64) == cd;
+      rank += (same && j < lane) ? 1u : 0u;
+      last = last && !(same && j > lane);
+    }
+    if (cd >= 0) list[bptr[cd] + (int64_t)(cur[cd] + rank)] = (int32_t)i;
+    __syncthreads();
+    if (cd >= 0 && last) cur[cd] += rank + 1u;
+    __syncthreads();
+  }
+}
+
+// grid.x = chunk * gene_blocks + gene block (neighbouring workgroups read neighbouring pieces of the same rows);
+// rng[2 ch], rng[2 ch + 1]: the chunk's span of the cell list (never empty).  COUNT: add 1 where x > 0 instead of x.
+template <typename T, bool COUNT>
+__global__ __launch_bounds__(256) void k_pb_dense(const T* __restrict__ X, int64_t G, int64_t gene_blocks,
+                                                  const int32_t* __restrict__ list, const int64_t* __restrict__ rng,
+                                                  double* __restrict__ part) {
+  constexpr int U = 8;
+  const int64_t ch = (int64_t)blockIdx.x / gene_blocks, gb = (int64_t)blockIdx.x % gene_blocks;
+  const int64_t g = gb * blockDim.x + threadIdx.x;
+  const bool act = g < G;
+  const int64_t gl = act ? g : G - 1;          // idle lanes of the last gene block reload its last gene; nothing is stored
+  const int64_t lo = rng[2 * ch], hi = rng[2 * ch + 1];
+  double acc = 0.0;
+  for (int64_t e = lo; e < hi; e += U) {
+    T xs[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t ee = e + u < hi ? e + u : hi - 1;
+      xs[u] = X[(int64_t)list[ee] * G + gl];   // list[ee] is the same in every lane: a scalar load
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (e + u >= hi) break;
+      acc += COUNT ? (xs[u] > (T)0 ? 1.0 : 0.0) : (double)xs[u];
+    }
+  }
+  if (act) part[ch * G + g] = acc;
+}
+
+// out[bin][gene] = the bin's partials added in chunk order (bfirst: first chunk of every bin, n_bins + 1 entries)
+__global__ __launch_bounds__(256) void k_pb_finish_dense(const double* __restrict__ part, int64_t G, int n_bins,
+                                                         const int64_t* __restrict__ bfirst, double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)n_bins * G) return;
+  const int64_t b = t / G, g = t % G;
+  double s = 0.0;
+  for (int64_t ch = bfirst[b]; ch < bfirst[b + 1]; ++ch) s += part[ch * G + g];
+  out[t] = s;
+}
+
+// one wave per chunk c0 + blockIdx.x of the gene lists; dynamic LDS: n_bins doubles (the sums) and n_bins ints (turns).
+// A batch is 64 consecutive entries.  Where every lane of a batch that takes part names the same bin, the wave adds them
+// by its fixed tree and lane 0 adds the total; otherwise rounds: every waiting lane posts stamp * 64 + 63 - lane with an
+// integer atomic max, the lowest waiting lane of each bin finds its own value there and adds.  Both orders depend on the
+// input alone.
+template <typename T, bool COUNT>
+__global__ __launch_bounds__(64) void k_pb_sparse(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
+                                                  const int64_t* __restrict__ gptr, int64_t c0, int64_t chunk_len,
+                                                  const int32_t* __restrict__ gcell, const T* __restrict__ gval,
+                                                  const int32_t* __restrict__ codes, int n_bins, double* __restrict__ part) {
+  extern __shared__ double pb_lds[];
+  double* acc = pb_lds;
+  int* turn = reinterpret_cast<int*>(pb_lds + n_bins);
+  const int lane = threadIdx.x;
+  const int64_t ch = c0 + blockIdx.x;
+  for (int b = lane; b < n_bins; b += 64) {
+    acc[b] = 0.0;
+    turn[b] = 0;
+  }
+  __syncthreads();
+  const int64_t lo = chunk_lo[ch];
+  const int64_t end = gptr[chunk_gene[ch] + 1];
+  const int64_t hi = lo + chunk_len < end ? lo + chunk_len : end;
+  int stamp = 0;
+  for (int64_t e0 = lo; e0 < hi; e0 += 64) {
+    const int64_t e = e0 + lane;
+    int32_t bin = -1;
+    double v = 0.0;
+    if (e < hi) {
+      bin = codes[gcell[e]];
+      const T x = gval[e];
+      v = COUNT ? (x > (T)0 ? 1.0 : 0.0) : (double)x;
+    }
+    bool wait = bin >= 0;
+    const unsigned long long in = __ballot(wait);
+    if (in == 0) continue;
+    const int32_t b0 = __shfl(bin, __ffsll((long long)in) - 1, 64);
+    if (__ballot(wait && bin != b0) == 0) {
+      const double s = wave_sum(wait ? v : 0.0);
+      if (lane == 0) acc[b0] += s;
+      __syncthreads();
+      continue;
+    }
+    while (true) {
+      ++stamp;
+      const int mine = stamp * 64 + 63 - lane;
+      if (wait) atomicMax(&turn[bin], mine);
+      __syncthreads();
+      if (wait && turn[bin] == mine) {
+        acc[bin] += v;
+        wait = false;
+      }
+      __syncthreads();
+      if (__ballot(wait) == 0) break;
+    }
+  }
+  __syncthreads();
+  double* o = part + (int64_t)blockIdx.x * n_bins;
+  for (int b = lane; b < n_bins; b += 64) o[b] = acc[b];
+}
+
+// genes [g0, g1) of a tile whose first chunk is c0: out[bin][gene] = the gene's partials added in chunk order
+__global__ __launch_bounds__(256) void k_pb_finish_sparse(const double* __restrict__ part, const int64_t* __restrict__ gchunk,
+                                                          int64_t g0, int64_t g1, int64_t c0, int n_bins, int64_t G,
+                                                          double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (g1 - g0) * n_bins) return;
+  const int64_t g = g0 + t / n_bins, b = t % n_bins;
+  double s = 0.0;
+  for (int64_t ch = gchunk[g]; ch < gchunk[g + 1]; ++ch) s += part[(ch - c0) * n_bins + b];
+  out[b * G + g] = s;
+}
+
+template <typename T>
+int pb_dense(cna_ctx* c, ExprState* s, int n_bins, bool count, const std::vector<int64_t>& tot) {
+  const int64_t n = s->n, G = s->G;
+  std::vector<int64_t> bptr((size_t)n_bins + 1, 0), first((size_t)n_bins + 1, 0), rng;
+  for (int b = 0; b < n_bins; ++b) {
+    bptr[(size_t)b + 1] = bptr[(size_t)b] + tot[(size_t)b];
+    first[(size_t)b] = (int64_t)rng.size() / 2;
+    for (int64_t e = bptr[(size_t)b]; e < bptr[(size_t)b + 1]; e += PB_DENSE_CHUNK) {
+      rng.push_back(e);
+      rng.push_back(std::min(e + PB_DENSE_CHUNK, bptr[(size_t)b + 1]));
+    }
+  }
+  const int64_t nch = (int64_t)rng.size() / 2;
+  first[(size_t)n_bins] = nch;
+  const int threads = (int)std::min<int64_t>(256, (G + 63) / 64 * 64);
+  const int64_t gene_blocks = (G + threads - 1) / threads;
+  if (nch * gene_blocks > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, "cna_expr_to_bins: more than 2^31 - 1 workgroups (chunks x gene blocks)");
+  CNA_TRY(buf_need(c, s, s->blist, 4 * n));
+  CNA_TRY(buf_need(c, s, s->bptr, 8 * ((int64_t)n_bins + 1)));
+  CNA_TRY(buf_need(c, s, s->bfirst, 8 * ((int64_t)n_bins + 1)));
+  CNA_TRY(buf_need(c, s, s->brng, 16 * std::max<int64_t>(1, nch)));
+  CNA_TRY(buf_need(c, s, s->part, 8 * std::max<int64_t>(1, nch) * G));
+  HIP_TRY(hipMemcpyAsync(s->bptr.p, bptr.data(), 8 * bptr.size(), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemcpyAsync(s->bfirst.p, first.data(), 8 * first.size(), hipMemcpyHostToDevice, s->st));
+  if (nch) HIP_TRY(hipMemcpyAsync(s->brng.p, rng.data(), 8 * rng.size(), hipMemcpyHostToDevice, s->st));
+  const int64_t rpb = round_up64((n + PB_MAX_BLOCKS - 1) / PB_MAX_BLOCKS, 64);
+  const unsigned B = (unsigned)((n + rpb - 1) / rpb);
+  hipLaunchKernelGGL(k_pb_fill, dim3(B), dim3(64), 0, s->st, (const int32_t*)s->bcode.p, n, n_bins, rpb,
+                     (const unsigned int*)s->bcnt.p, (const int64_t*)s->bptr.p, (int32_t*)s->blist.p);
+  if (nch) {
+    const dim3 grid((unsigned)(nch * gene_blocks));
+    if (count)
+      hipLaunchKernelGGL((k_pb_dense<T, true>), grid, dim3(threads), 0, s->st, (const T*)s->X.p, G, gene_blocks,
+                         (const int32_t*)s->blist.p, (const int64_t*)s->brng.p, (double*)s->part.p);
+    else
+      hipLaunchKernelGGL((k_pb_dense<T, false>), grid, dim3(threads), 0, s->st, (const T*)s->X.p, G, gene_blocks,
+                         (const int32_t*)s->blist.p, (const int64_t*)s->brng.p, (double*)s->part.p);
+  }
+  hipLaunchKernelGGL(k_pb_finish_dense, dim3((unsigned)(((int64_t)n_bins * G + 255) / 256)), dim3(256), 0, s->st,
+                     (const double*)s->part.p, G, n_bins, (const int64_t*)s->bfirst.p, (double*)s->rout.p);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int pb_sparse(cna_ctx* c, ExprState* s, int n_bins, bool count) {
+  const int64_t G = s->G;
+  const int64_t max_chunks = std::max<int64_t>(1, PB_PART_BYTES / (8 * (int64_t)n_bins));
+  const std::vector<int64_t>& gc = s->gchunk_h;
+  // tiles of whole genes, each with at most max_chunks chunks (one gene at least)
+  int64_t need = 1;
+  for (int64_t g0 = 0; g0 < G;) {
+    int64_t g1 = g0 + 1;
+    while (g1 < G && gc[(size_t)g1 + 1] - gc[(size_t)g0] <= max_chunks) ++g1;
+    need = std::max(need, gc[(size_t)g1] - gc[(size_t)g0]);
+    g0 = g1;
+  }
+  if (need > 0x7fffffffll / 256) CNA_FAIL(CNA_EINVAL, "cna_expr_to_bins: one gene has too many chunks");
+  CNA_TRY(buf_need(c, s, s->part, 8 * need * n_bins));
+  const size_t lds = (size_t)n_bins * 12;
+  for (int64_t g0 = 0; g0 < G;) {
+    int64_t g1 = g0 + 1;
+    while (g1 < G && gc[(size_t)g1 + 1] - gc[(size_t)g0] <= max_chunks) ++g1;
+    const int64_t c0 = gc[(size_t)g0], nch = gc[(size_t)g1] - c0;
+    if (nch) {
+      if (count)
+        hipLaunchKernelGGL((k_pb_sparse<T, true>), dim3((unsigned)nch), dim3(64), lds, s->st, (const int64_t*)s->chunk_lo.p,
+                           (const int32_t*)s->chunk_gene.p, (const int64_t*)s->gptr.p, c0, s->chunk_len,
+                           (const int32_t*)s->gcell.p, (const T*)s->gval.p, (const int32_t*)s->bcode.p, n_bins,
+                           (double*)s->part.p);
+      else
+        hipLaunchKernelGGL((k_pb_sparse<T, false>), dim3((unsigned)nch), dim3(64), lds, s->st, (const int64_t*)s->chunk_lo.p,
+                           (const int32_t*)s->chunk_gene.p, (const int64_t*)s->gptr.p, c0, s->chunk_len,
+                           (const int32_t*)s->gcell.p, (const T*)s->gval.p, (const int32_t*)s->bcode.p, n_bins,
+                           (double*)s->part.p);
+    }
+    hipLaunchKernelGGL(k_pb_finish_sparse, dim3((unsigned)(((g1 - g0) * n_bins + 255) / 256)), dim3(256), 0, s->st,
+                       (const double*)s->part.p, (const int64_t*)s->gchunk.p, g0, g1, c0, n_bins, G, (double*)s->rout.p);
+    g0 = g1;
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 void expr_destroy(cna_ctx* c) {
@@ -807,6 +1078,45 @@ int cna_gene_corr(cna_ctx* c, const double* V, int q, double* r_out) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(r_out, s->rout.p, (size_t)(8 * G * q), hipMemcpyDeviceToHost, s->st));
   HIP_TRY(hipStreamSynchronize(s->st));
+  return 0;
+}
+
+int cna_expr_to_bins(cna_ctx* c, const int32_t* codes, int n_bins, int what, double* sums_out, int64_t* counts_out) {
+  CHECK_CTX(c);
+  ExprState* s = state_of(c);
+  if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_expr_to_bins: no expression matrix is resident (cna_expr_upload_*)");
+  if (!codes || !sums_out || !counts_out) CNA_FAIL(CNA_EINVAL, "cna_expr_to_bins: null pointer");
+  if (n_bins < 1 || n_bins > PB_MAX_BINS) CNA_FAIL(CNA_EINVAL, "cna_expr_to_bins: 1 <= n_bins <= 4096");
+  if (what != 0 && what != 1) CNA_FAIL(CNA_EINVAL, "cna_expr_to_bins: what is 0 (sums of x) or 1 (counts of x > 0)");
+  const int64_t n = s->n, G = s->G;
+  const int64_t rpb = round_up64((n + PB_MAX_BLOCKS - 1) / PB_MAX_BLOCKS, 64);
+  const int64_t B = (n + rpb - 1) / rpb;
+  CNA_TRY(buf_need(c, s, s->bcode, 4 * n));
+  CNA_TRY(buf_need(c, s, s->bcnt, 4 * B * n_bins));
+  CNA_TRY(buf_need(c, s, s->btot, 8 * (int64_t)n_bins));
+  CNA_TRY(buf_need(c, s, s->flag, 256));
+  CNA_TRY(buf_need(c, s, s->rout, 8 * G * n_bins));
+  HIP_TRY(hipMemcpyAsync(s->bcode.p, codes, (size_t)(4 * n), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemsetAsync(s->flag.p, 0, 4, s->st));
+  hipLaunchKernelGGL(k_pb_count, dim3((unsigned)B), dim3(256), 0, s->st, (const int32_t*)s->bcode.p, n, n_bins, rpb,
+                     (unsigned int*)s->bcnt.p, (int*)s->flag.p);
+  hipLaunchKernelGGL(k_tr_scan, dim3((unsigned)((n_bins + 255) / 256)), dim3(256), 0, s->st, (unsigned int*)s->bcnt.p,
+                     (int64_t)n_bins, (int)B, (int64_t*)s->btot.p);
+  HIP_TRY(hipGetLastError());
+  // the codes are judged before any sum is formed
+  int bad = 0;
+  std::vector<int64_t> tot((size_t)n_bins);
+  HIP_TRY(hipMemcpyAsync(&bad, s->flag.p, 4, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipMemcpyAsync(tot.data(), s->btot.p, 8 * (size_t)n_bins, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  if (bad) CNA_FAIL(CNA_EINVAL, "cna_expr_to_bins: a code lies outside [-1, n_bins)");
+  if (s->format == 1)
+    CNA_TRY(s->is_f64 ? pb_dense<double>(c, s, n_bins, what == 1, tot) : pb_dense<float>(c, s, n_bins, what == 1, tot));
+  else
+    CNA_TRY(s->is_f64 ? pb_sparse<double>(c, s, n_bins, what == 1) : pb_sparse<float>(c, s, n_bins, what == 1));
+  HIP_TRY(hipMemcpyAsync(sums_out, s->rout.p, (size_t)(8 * G * n_bins), hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  std::memcpy(counts_out, tot.data(), 8 * (size_t)n_bins);
   return 0;
 }
 

@@ -1214,6 +1214,20 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_gene_corr(self.h, ptr(V), V.shape[0], ptr(out)), 'cna_gene_corr')
         return out
 
+    def expr_to_bins(self, codes, n_bins, what):
+        """Per-bin sums of the resident expression matrix (cna_expr_to_bins): `codes` int32 per cell in the caller's
+        order, -1 = cell left out; `what` 0 sums x, 1 counts x > 0.  Returns (sums float64[n_bins, genes],
+        counts int64[n_bins] of cells per bin)."""
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        info = self.expression_shape()
+        if info['format'] != 'none' and codes.shape != (info['n_cells'],):
+            raise ValueError('expr_to_bins: %d codes for %d resident cells' % (codes.size, info['n_cells']))
+        n_bins = int(n_bins)
+        sums = np.empty((max(n_bins, 0), info['n_genes']))
+        counts = np.empty(max(n_bins, 0), dtype=np.int64)
+        check(self.lib.cna_expr_to_bins(self.h, ptr(codes), n_bins, int(what), ptr(sums), ptr(counts)), 'cna_expr_to_bins')
+        return sums, counts
+
     # ---------------------------------------------------------------- synthetic inputs
     def knn_graph(self, X, k):
         """scanpy-like connectivities of the points X (n x d, d <= 64) built on the device

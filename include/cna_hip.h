@@ -612,6 +612,24 @@ int  cna_expr_shape(cna_ctx* ctx, int64_t* n_cells, int64_t* n_genes, int64_t* n
  * CNA_ESTATE: no expression matrix is resident. */
 int  cna_gene_corr(cna_ctx* ctx, const double* V, int q, double* r_out);
 
+/* ---- per-bin sums of the resident expression matrix (csrc/genes.hip) ------------------------- */
+/* The sample-level side of the reference's workflow: utils/multisample.py:4-11 (obs_to_sample) turns per-cell columns of
+ * d.obs into one row per sample; this is the same aggregation for d.X, the samples x genes matrix of summed expression
+ * ("pseudobulk"), over the matrix cna_expr_upload_* left on the device, dense or gene-major.  codes[i] is the bin (row of
+ * the result) of cell i in the CALLER's cell order, -1 for a cell that is left out; 1 <= n_bins <= 4096.
+ *   what = 0: sums_out[b * n_genes + g] = sum of x[i, g] over the cells of bin b
+ *   what = 1: ... = number of those cells with x[i, g] > 0 (an explicit zero of a sparse upload does not count)
+ * counts_out[b] = cells of bin b.  The means and fractions of cna.ut.expr_to_sample are these over counts_out, divided
+ * by the caller in float64: the device returns sums and integers only.  Sums are float64 in a fixed order (the cells of a
+ * bin ascending, cut into chunks whose partials are added in chunk order; no floating-point atomics): two runs give the
+ * same bits, and so do a CSR and a CSC upload of one matrix.  A bin without cells gives 0; NaN / inf inside X reach
+ * their own (bin, gene) only.
+ * Like cna_gene_corr it runs on the expression stream with buffers of its own (grow-only, freed by cna_expr_drop), works on
+ * a context that never saw a graph, and may be called between cna_null_local_launch and cna_null_local_fetch.
+ * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL: n_bins or what out of range, or a code outside
+ * [-1, n_bins) -- found on the device before any sum is formed; nothing is written then. */
+int  cna_expr_to_bins(cna_ctx* ctx, const int32_t* codes, int n_bins, int what, double* sums_out, int64_t* counts_out);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
  * on = 2: the walk kernels (CNA_K_NAM_FIRST / _STEP / _STEP_SPARSE) and the communication spans only -- two event records
