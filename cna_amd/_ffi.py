@@ -140,6 +140,9 @@ SIGNATURES = {
     'cna_expr_shape': (C.c_int, [c_ctx, c_i64p, c_i64p, c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_i64p]),
     'cna_gene_corr': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p]),
     'cna_expr_to_bins': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'cna_expr_cross': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_int64)]),
+    'cna_x_generation': (C.c_int, [c_ctx, C.POINTER(C.c_int64)]),
 }
 
 MAT_NAM, MAT_X, MAT_PROJ = 0, 1, 2

@@ -420,6 +420,24 @@ class CellOrder:
                 self._kept_order_cache = pos[inv[np.flatnonzero(kept_user)]]
         return self._kept_order_cache
 
+    def x_row_of_cells(self):
+        """Row of the working matrix X of every cell in the caller's order, -1 for a cell the selection dropped (int64;
+        one rank, replicated view) -- the inverse of what `kept_to_user` gathers with."""
+        n = int(self.n)
+        if not self._x_is_selection:                       # upload_x: rows in the caller's order already
+            return np.arange(int(self.x_rows_total), dtype=np.int64)
+        if self.perm is None:
+            if self._keep_dev is None:
+                return np.arange(n, dtype=np.int64)
+            out = np.full(n, -1, dtype=np.int64)
+            out[np.flatnonzero(self._keep_dev)] = np.arange(int(np.count_nonzero(self._keep_dev)), dtype=np.int64)
+            return out
+        if self._keep_dev is None:
+            return np.ascontiguousarray(self._kept_order(), dtype=np.int64)
+        out = np.full(n, -1, dtype=np.int64)
+        out[np.sort(self.perm[self._keep_dev])] = self._kept_order()
+        return out
+
     def kept_to_user(self, m):
         if self.perm is None or not self._x_is_selection:
             return m

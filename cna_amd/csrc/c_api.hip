@@ -119,6 +119,7 @@ static void void_x(cna_ctx* c) {          // X and everything derived from it
   c->gram_n = 0;
   c->cells.coef_early = false;
   c->cells.fdr_inline = false;
+  c->x_gen = c->x_gen + 1;                // (what callers key their own memos of X-derived results with: cna_x_generation)
 }
 static void void_walk(cna_ctx* c) {       // the walk (state, NAM), then X
   c->t_valid = c->nam_valid = c->nam_lazy = false;
@@ -325,6 +326,12 @@ int cna_ctx_sync(cna_ctx* c) {
 int cna_ctx_device_bytes(cna_ctx* c, int64_t* bytes) {
   if (!c || !bytes) CNA_FAIL(CNA_EINVAL, "null argument");
   *bytes = c->dev_bytes.load();
+  return 0;
+}
+
+int cna_x_generation(cna_ctx* c, int64_t* gen) {
+  if (!c || !gen) CNA_FAIL(CNA_EINVAL, "null argument");
+  *gen = c->x_gen;
   return 0;
 }
 

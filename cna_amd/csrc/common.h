@@ -218,6 +218,8 @@ struct cna_ctx {
   int64_t* keep_store = nullptr;  // allocation behind keep_idx
   int64_t keep_cap = 0;
   bool x_valid = false, x_from_nam = false;   // [void_x]
+  int64_t x_gen = 0;               // [void_x] counts the times X was voided (cna_x_generation): a caller's memo of something
+                                   //   derived from X (engine.expr_cross) holds while this stands still
   bool x_ident = false;            // [void_x] X = standardised NAM, every cell, samples in place, nothing regressed out (cna_x_identity)
   // The selection pass as a by-product of the walk's last step (cna_nam_select_hint): when the caller says which
   // standardised phenotype the analysis will use and nothing will be filtered or regressed out, the last step's
@@ -306,7 +308,8 @@ struct cna_ctx {
   int64_t gram_tiles_cap = 0;
 
   // ---- resident expression matrix and the work buffers of cna_gene_corr (genes.hip owns all of it: caller's cell order,
-  // a stream of its own; derived from nothing above, so none of the transitions of c_api.hip concerns it)
+  // a stream of its own; derived from nothing above, so none of the transitions of c_api.hip concerns it.  cna_expr_cross
+  // reads X from there, keeps nothing derived from it and returns only once its stream has drained)
   void* expr = nullptr;
 
   // ---- profiling

@@ -53,6 +53,8 @@ class Engine(_order.CellOrder):
         self._graph_ref = None
         self._pinned = None
         self._expr_key = self._expr_hash = self._expr_ref = self._expr_pinned = None
+        self._cross_memo = None     # (key, content signature, result) of the last expr_cross
+        self.cross_launches = 0     # cna_expr_cross calls so far (a memo hit launches nothing)
         self._host_threads = _order.usable_cpus(8)
         self._colsum_w = None
         self._codes_token = self._codes_graph = None
@@ -693,6 +695,16 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_gram_fetch(self.h, ptr(G)), 'cna_gram_fetch')
         return G
 
+    def gram_held(self):
+        """The Gram matrix X^T X of the current working matrix as the library still holds it from the last launch (an
+        analysis leaves it there), else launched now -- on the device either way, never from a fetched X."""
+        cols = self.matrix_shape(MAT_X)[1]
+        G = np.empty((cols, cols))
+        if self.lib.cna_gram_fetch(self.h, ptr(G)) != 0:       # voided, or of another order: take it again
+            check(self.lib.cna_gram(self.h, ptr(G)), 'cna_gram')
+        self._gram_cols = cols
+        return G
+
     def gram_pcs_tests(self, ks, r, native=True, resid_tol=1e-12, gap_tol=1e-6):
         """gram_fetch(), the leading max(ks) eigenpairs on the host and -- when the library's own solver is accepted
         (tools/_nam.py:_top_pcs_native's rule) -- global_test_launch(), in ONE call without the interpreter in between.
@@ -1147,6 +1159,7 @@ class Engine(_order.CellOrder):
     def drop_expression(self):
         """Forget the resident expression matrix and free its device memory: the next call uploads afresh."""
         self._expr_key = self._expr_hash = self._expr_ref = None
+        self._cross_memo = None
         check(self.lib.cna_expr_drop(self.h), 'cna_expr_drop')
 
     def ensure_expression(self, X):
@@ -1227,6 +1240,62 @@ class Engine(_order.CellOrder):
         counts = np.empty(max(n_bins, 0), dtype=np.int64)
         check(self.lib.cna_expr_to_bins(self.h, ptr(codes), n_bins, int(what), ptr(sums), ptr(counts)), 'cna_expr_to_bins')
         return sums, counts
+
+    def x_generation(self):
+        """How often the library has voided the working matrix X so far (cna_x_generation: every producer of X and every
+        transition above it, in place or not)."""
+        g = C.c_int64(0)
+        check(self.lib.cna_x_generation(self.h, C.byref(g)), 'cna_x_generation')
+        return g.value
+
+    def expr_cross(self, content=None, xrow=None):
+        """(W, rho, sx, sxx, m) of the resident expression matrix E against the working matrix X (cna_expr_cross):
+        W = E_K^T X (genes x samples float64), rho the column sums of X, sx / sxx the per-gene sums of x and x^2, all over
+        the m cells that have a row in X (`x_row_of_cells`: the caller's order against the device order and the
+        selection).  One rank, replicated view.
+
+        Memo: the result is kept under (uploads of the expression matrix, x_epoch, the library's X generation) -- every
+        transition that voids what is derived from X moves the last of them (csrc/c_api.hip:void_x) -- and a call under
+        the same key launches nothing (`cross_launches` counts the launches).  `content`: the caller's word for what X
+        was made from (cna.tl.gene_test: the NAM's signature, the kept cells, the samples, the projector and the Gram
+        matrix' bits); a further analysis rebuilds X, so the key moves, but under an equal `content` the X is the same
+        and the memo is carried over to the new key instead of being taken again.  (x_epoch alone cannot serve a second
+        phenotype: every association selects and residualises anew, so X is rebuilt -- to the same bits -- and the epoch
+        moves with every call.)  `cross_extra()` is a dict that lives and dies with the memo, for what else a caller
+        derives from the same E and the same cells.  `xrow`: an explicit map instead of `x_row_of_cells()`; such a call
+        neither reads nor writes the memo."""
+        if self.nranks != 1 or self.view_local:
+            raise NotImplementedError('expr_cross needs every row of X on this rank (one rank, replicated view)')
+        info = self.expression_shape()
+        key = (info['uploads'] if info['format'] != 'none' else None, self.x_epoch, self.x_generation())
+        memo = self._cross_memo
+        if memo is not None and key[0] is not None and xrow is None:
+            if memo[0] == key:
+                return memo[2]
+            if content is not None and memo[1] == content and memo[0][0] == key[0]:
+                self._cross_memo = (key, content, memo[2], memo[3])
+                return memo[2]
+        g = info['n_genes']
+        cols = self.matrix_shape(MAT_X)[1] if info['format'] != 'none' else 0
+        explicit = xrow is not None
+        xrow = np.ascontiguousarray(xrow if explicit else self.x_row_of_cells(), dtype=np.int64)
+        W, rho = np.empty((g, cols)), np.empty(cols)
+        sx, sxx = np.empty(g), np.empty(g)
+        m = C.c_int64(0)
+        self.cross_launches += 1
+        check(self.lib.cna_expr_cross(self.h, ptr(xrow), len(xrow), ptr(W), ptr(rho), ptr(sx), ptr(sxx), C.byref(m)),
+              'cna_expr_cross')
+        out = (W, rho, sx, sxx, int(m.value))
+        if explicit:
+            return out
+        for a in out[:4]:
+            a.setflags(write=False)
+        self._cross_memo = (key, content, out, {})
+        return out
+
+    def cross_extra(self):
+        """The dict that goes with the current expr_cross memo (empty after every launch, gone with the memo)."""
+        return {} if self._cross_memo is None else self._cross_memo[3]
 
     # ---------------------------------------------------------------- synthetic inputs
     def knn_graph(self, X, k):

@@ -34,6 +34,7 @@ from ._stats import conditional_permutation, grouplevel_permutation, default_ks,
 
 
 _pool = None
+_tolerate = threading.local()      # .no_fdr: set by cna.tl.gene_test around its association call (see _association_call's end)
 
 
 def _background():
@@ -1050,9 +1051,10 @@ def _association_call(data, y, sid_name, batches, covs, donorids, ks, key_added,
         # cohort, a failed draw, an interrupt): collect and drop it, or every later call on this engine finds it pending
         _drop_pending_null(engine)
         raise
-    if fdr_all is None:
+    if fdr_all is None and not getattr(_tolerate, 'no_fdr', False):
         # upstream has written data.obs[key_added] and then dereferences res.fdrs, which is None when
         # local_test=False (_association.py:231,235): same state of data.obs, same exception
+        # (cna.tl.gene_test, which has no use for the FDR table, asks for the result instead: _tolerate.no_fdr)
         raise AttributeError("'NoneType' object has no attribute 'loc'")
 
     if return_full:

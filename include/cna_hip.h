@@ -630,6 +630,32 @@ int  cna_gene_corr(cna_ctx* ctx, const double* V, int q, double* r_out);
  * [-1, n_bins) -- found on the device before any sum is formed; nothing is written then. */
 int  cna_expr_to_bins(cna_ctx* ctx, const int32_t* codes, int n_bins, int what, double* sums_out, int64_t* counts_out);
 
+/* ---- the expression matrix against the working matrix (csrc/genes.hip) ------------------------ */
+/* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
+ * z_p (_association.py:94-99; the observed one is _association.py:77 with z = the standardised y), the correlation of
+ * gene g with c_p -- demo/demo.ipynb's "per-gene correlations to neighborhood coefficient" under the null -- needs
+ *   sum_i x[i,g] c_p[i] = (W_g . z_p) / N,   sum_i c_p[i] = (rho . z_p) / N,   sum_i c_p[i]^2 = z_p^T (X^T X) z_p / N^2
+ * so one contraction over the cells serves every permutation of every phenotype on the same covariates:
+ *   W_out[g * n_cols + s] = sum over the cells i with xrow[i] >= 0 of x[i,g] * X[xrow[i]][s]      (n_genes x n_cols)
+ *   rho_out[s] = sum over those cells of X[xrow[i]][s];  sx_out[g], sxx_out[g] = their sums of x[i,g] and x[i,g]^2
+ *   *m_out = their number
+ * X is the working matrix (CNA_MAT_X: rows x n_cols float64, n_cols <= 1024), read and left as it is; xrow[i] is the row
+ * of X of cell i of the expression matrix (CALLER's cell order, n_cells entries), -1 for a cell that has none (the
+ * selection dropped it).  xrow is checked on the device before any sum is formed: CNA_EINVAL, with nothing written, for a
+ * value outside [-1, rows of X), a row of X named twice, or n_cells other than the resident matrix' cells.  CNA_ESTATE: no
+ * expression matrix, no X, or a context with a communicator (the rows of other ranks are elsewhere).  The f32 state
+ * switch (cna_set_state_f32) is supported: it concerns the walk's state only, X is float64 either way.
+ * Sums are float64 in a fixed order (dense: the cells of a slab ascending, slabs in order; gene-major lists: a gene's
+ * entries ascending, chunks in order; no floating-point atomics): two runs give the same bits, and so do a CSR and a CSC
+ * upload of one matrix.  Runs on the expression stream with grow-only buffers of its own (freed by cna_expr_drop) and
+ * changes no other state; it waits there, through an event, for what the main stream has queued that produces X, and
+ * returns only after its own stream has drained, so a later producer of X finds the read finished.  May be called between cna_null_local_launch and cna_null_local_fetch (both read X). */
+int  cna_expr_cross(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, double* W_out, double* rho_out, double* sx_out,
+                    double* sxx_out, int64_t* m_out);
+/* Counts the times the working matrix X and what is derived from it were voided (every producer of X, every transition
+ * above it): a caller that keeps something derived from X (cna_expr_cross' result) may keep it while this stands still. */
+int  cna_x_generation(cna_ctx* ctx, int64_t* gen);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
  * on = 2: the walk kernels (CNA_K_NAM_FIRST / _STEP / _STEP_SPARSE) and the communication spans only -- two event records
