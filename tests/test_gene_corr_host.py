@@ -224,16 +224,34 @@ def test_single_nonzero_gene_has_a_closed_form():
     assert abs(got[0] - want) <= 1e-13 and abs(got[1] - 1.0) <= 1e-13
 
 
-@pytest.mark.parametrize('seed', [0, 1, 2])
+PARITY_Q = [1, 2, 3, 5, 8, 16]      # key counts of the GPU parity cases; each also seeds its expression matrix and its keys
+
+
+@pytest.mark.parametrize('seed', sorted(set([0, 1, 2] + PARITY_Q)))
 def test_parity_inputs_are_benign_for_raw_moments(seed, demo):
     """The inputs the GPU tests use for parity: sum x^2 / sum (x - mean)^2 <= 100 for every non-constant gene, so that
-    their 1e-10 bound tests the kernels and not the raw-moment formula."""
+    their 1e-10 bound tests the kernels and not the raw-moment formula.  For the key counts of PARITY_Q the matrices are
+    the GPU cases' own (3001 x 70, seed = q), and the figure is taken again over the cells every key of every mask layout
+    keeps -- the sums the kernels form."""
     assert conditioning(demo.X) <= 5
     for n, g in ((3001, 70), (1000, 33)):
         assert conditioning(sparse_expression(n, g, seed=seed)) <= 100
     assert conditioning(dense_expression(3001, 70, seed)) <= 100
     M = big_sparse_expression(2000, 400, per_row=20, seed=seed)
     assert conditioning(M) <= 100 and M.has_canonical_format
+    if seed in PARITY_Q:
+        q = seed
+        Xs = (dense_expression(3001, 70, seed=q), dense_expression(3001, 70, seed=q, dtype=np.float32).astype(np.float64),
+              sparse_expression(3001, 70, seed=q).toarray())
+        for masks in ('none', 'equal', 'differ'):
+            V = keys_for(3001, q, seed=q, masks=masks)
+            assert V.shape == (q, 3001)
+            kept = np.unique(np.isfinite(V), axis=0)
+            assert len(kept) == (1 if masks != 'differ' or q == 1 else q) and (kept.sum(axis=1) > 2500).all()
+            for w in kept:
+                for X in Xs:
+                    assert conditioning(X[w]) <= 100, (q, masks)
+            # the keys themselves are centred before they are multiplied (k_key_stats, k_key_table): nothing to condition
 
 
 def dense_expression(n, g, seed=0, dtype=np.float64):

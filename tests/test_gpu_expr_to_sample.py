@@ -152,6 +152,28 @@ def test_refusals_leave_the_matrix_usable(eng):
         assert full[1].sum() == 1000
 
 
+def test_second_gene_tile_of_the_gene_major_kernel(eng):
+    """4096 bins leave pb_sparse 8192 chunks per gene tile; 418 genes present in each of 20 517 cells are 8778 chunks of 1024
+    entries: two tiles, an empty gene closing the first (tests/test_expr_tiles_host.py builds the input and asserts that).
+    Integer-valued, so sums, counts of x > 0 and cell counts equal the restatement bit for bit."""
+    from test_expr_tiles_host import bins_tile_case, assert_bins_tile_case, BINS_BINS
+    M, codes = bins_tile_case()
+    assert_bins_tile_case(M)
+    D = M.toarray()
+    want, wcnt = restated_bins(D, codes, BINS_BINS, 0)
+    # restated_bins(.., what=1) compares the whole matrix with 0 once per bin; the same figure from the comparison made once
+    want_pos = restated_bins((D > 0).astype(np.float64), codes, BINS_BINS, 0)[0]
+    assert (wcnt == 0).any() and (want_pos != want).any()
+    for form in ('csr-i32', 'csc-i64'):
+        X = as_form(M, form)
+        assert X.nnz == M.nnz                                        # the stored zeros stay stored
+        for what, ref in ((0, want), (1, want_pos)):
+            got, cnt = _bins(eng, X, codes, BINS_BINS, what)
+            np.testing.assert_array_equal(cnt, wcnt, err_msg=form)
+            np.testing.assert_array_equal(got, ref, err_msg='%s what=%d' % (form, what))
+    eng.drop_expression()
+
+
 # ------------------------------------------------------------------ 2. rounding
 def _real(n, g, seed, dtype):
     rs = np.random.RandomState(seed)

@@ -15,7 +15,7 @@ import pytest
 import scipy.sparse as sp
 
 from test_gene_corr_host import (restated_gene_corr, demo_line, sparse_expression, dense_expression, big_sparse_expression,
-                                 keys_for)
+                                 keys_for, PARITY_Q)
 
 pytestmark = pytest.mark.gpu
 
@@ -74,10 +74,13 @@ def test_the_demo_line(eng):
 
 # ------------------------------------------------------------------ 2. against the restatement
 N_ODD = 3001      # prime-ish: a multiple of no slab, chunk or unroll size
+# PARITY_Q = [1, 2, 3, 5, 8, 16] key columns: the kernels are instantiated for Q = 1, 2, 4, 8, 16 slots, so 2 runs Q = 2, 3 runs
+# Q = 4 with one padded slot, 5 runs Q = 8 with three, 8 runs Q = 8 full -- each on the dense and the gene-major kernel, with
+# one shared mask ('none', 'equal') and with one per key ('differ')
 
 
 @pytest.mark.parametrize('masks', ['none', 'equal', 'differ'])
-@pytest.mark.parametrize('q', [1, 3, 16])
+@pytest.mark.parametrize('q', PARITY_Q)
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_dense_against_restatement(eng, dtype, q, masks):
     X = dense_expression(N_ODD, 70, seed=q, dtype=dtype)
@@ -86,7 +89,7 @@ def test_dense_against_restatement(eng, dtype, q, masks):
 
 
 @pytest.mark.parametrize('masks', ['none', 'equal', 'differ'])
-@pytest.mark.parametrize('q', [1, 3, 16])
+@pytest.mark.parametrize('q', PARITY_Q)
 @pytest.mark.parametrize('fmt,index_dtype,dtype', [('csr', np.int32, np.float32), ('csr', np.int64, np.float64),
                                                    ('csc', np.int32, np.float64), ('csc', np.int64, np.float32)])
 def test_sparse_against_restatement(eng, fmt, index_dtype, dtype, q, masks):

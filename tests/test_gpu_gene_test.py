@@ -13,7 +13,18 @@ fixed-order float64 sums of the same m terms (tests/test_gpu_expr_to_sample.py u
 rounding of each product, which the FMA does not even commit).  Integer-valued inputs: bit-exact.  End to end: r against
 gene_corr and null_r against the materialised oracle within 100 x the CPU difference of tests/test_gene_test_host.py
 (4.441e-16, profiles/r09_gene_test_parity.txt), never looser than 1e-8.  The largest figures seen go to the file
-CNA_GENE_TEST_GPU_OUT names, when it is set."""
+CNA_GENE_TEST_GPU_OUT names, when it is set.
+
+The sample axis and the host loops (profiles/r10_gene_cross_wide_parity.txt).  cna_expr_cross branches on the number of
+samples: k_xc_sparse<T, P> holds P = 1, 2, 4, 8, 16 accumulators per lane for up to 64, 128, 256, 512, 1024 samples, k_xc_dense
+takes tiles of 32 samples (the last one ragged or full), k_xc_rho keeps four accumulators per thread (samples t, t + 256, ...),
+and the row stride of X differs from the sample count where that is no multiple of 4.  WIDE_N walks both sides of each of
+these at 2200 cells -- gene 0 present in every cell: chunks of 1024, 1024 and 152 entries, the last batch ragged; 17 slabs of
+the dense kernel -- through an explicit xrow (a permutation of the rows of a shorter X, a tenth of the cells -1): integer-
+valued inputs bit for bit at every count, real-valued ones against np.longdouble under the bound above at 65, 200 and 1024.
+Beside them: NaN and Inf stay in their own gene (and out of every sum when their cell has no row in X), a second gene tile
+of xc_sparse (tests/test_expr_tiles_host.py builds the input and proves its reach), k_xc_check's verdicts and k_xc_rho where
+1.1 million cells take the grid-stride loop and 1024 blocks, and one end-to-end call at 130 samples."""
 import ctypes as C
 import os
 import warnings
@@ -101,23 +112,31 @@ def analysed(eng, kind, **kw):
     return data, res
 
 
-def check_sums(tag, eng, E_used, kept, out):
-    """out = engine.expr_cross() against longdouble numpy on E_used (the values the device holds, cells x genes)."""
-    W, rho, sx, sxx, m = out
-    X = eng.x_full()                                                   # kept cells x samples, caller's order
-    assert X.shape[0] == int(kept.sum()) and m == X.shape[0]
-    EK = E_used[kept].astype(np.longdouble)
-    XL = X.astype(np.longdouble)
+def reference_sums(EK, XK):
+    """[(name, want, sum of |terms|)] of W, rho, sx, sxx in np.longdouble: EK the cells that take part x genes, XK their rows
+    of X."""
+    EK, XL = EK.astype(np.longdouble), XK.astype(np.longdouble)
+    return [('W', EK.T @ XL, np.abs(EK).T @ np.abs(XL)), ('rho', XL.sum(axis=0), np.abs(XL).sum(axis=0)),
+            ('sx', EK.sum(axis=0), np.abs(EK).sum(axis=0)), ('sxx', (EK * EK).sum(axis=0), (EK * EK).sum(axis=0))]
+
+
+def check_against(tag, ref, m, out):
+    """out[:4] against reference_sums' figures: |got - want| <= 2 (m - 1) 2^-52 sum |terms|."""
     u = 2.0 * (m - 1) * 2.0 ** -52
-    for name, got, want, mag in (('W', W, EK.T @ XL, np.abs(EK).T @ np.abs(XL)),
-                                 ('rho', rho, XL.sum(axis=0), np.abs(XL).sum(axis=0)),
-                                 ('sx', sx, EK.sum(axis=0), np.abs(EK).sum(axis=0)),
-                                 ('sxx', sxx, (EK * EK).sum(axis=0), (EK * EK).sum(axis=0))):
+    for (name, want, mag), got in zip(ref, out[:4]):
         err = np.abs(got.astype(np.longdouble) - want).astype(np.float64)
         bound = (u * mag).astype(np.float64)
         ratio = float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))))
         _note('%s %s: max |err| / bound' % (tag, name), ratio)
         assert ratio <= 1.0, (tag, name, ratio)
+
+
+def check_sums(tag, eng, E_used, kept, out):
+    """out = engine.expr_cross() against longdouble numpy on E_used (the values the device holds, cells x genes)."""
+    X = eng.x_full()                                                   # kept cells x samples, caller's order
+    m = out[4]
+    assert X.shape[0] == int(kept.sum()) and m == X.shape[0]
+    check_against(tag, reference_sums(E_used[kept], X), m, out)
 
 
 @pytest.mark.parametrize('form', FORMS)
@@ -445,3 +464,223 @@ def test_without_the_local_test(eng):
     assert d1.obs['coef'].values.tobytes() == d2.obs['coef'].values.tobytes()
     assert np.max(np.abs(n1 - n2)[np.arange(70) != 1]) <= R_TOL and np.max(np.abs(f1['r'] - f2['r']).values[np.arange(70) != 1]) <= R_TOL
     assert f1.attrs['p'] == f2.attrs['p']
+
+
+# ------------------------------------------------------------------ the sample axis: every P of k_xc_sparse, 2 to 32 dense tiles
+WIDE_N = [64, 65, 100, 128, 129, 200, 256, 257, 512, 513, 1024]
+WIDE_CELLS = 2200
+
+
+def wide_case(N, G, integer, seed=0):
+    """(E, X, xrow): E as expression() makes it, but gene 0 present in every cell (gene 1 stays empty) and, real-valued,
+    rounded to float32 so that the four forms hold the same values; X with fewer rows than there are cells; xrow a random
+    permutation of X's rows on nine cells in ten, -1 on the others."""
+    n = WIDE_CELLS
+    rs = np.random.RandomState(1000 * N + G + seed)
+    E = expression(n, G, seed=N + G + seed, integer=integer)
+    E[:, 0] = rs.randint(1, 10, n) if integer else 0.5 + rs.gamma(2.0, 1.0, n)
+    if not integer:
+        E = E.astype(np.float32).astype(np.float64)
+    took = rs.rand(n) < 0.9
+    nx = int(took.sum())
+    X = rs.randint(-3, 4, (nx, N)).astype(np.float64) if integer else rs.randn(nx, N) * (1.0 + rs.rand(N)) + rs.randn(N)
+    xrow = np.full(n, -1, dtype=np.int64)
+    xrow[took] = rs.permutation(nx)
+    assert nx < n and (E[:, 0] != 0).all() and not E[:, 1].any()
+    return E, X, xrow
+
+
+def _integer_want(E, X, xrow):
+    keep = xrow >= 0
+    EK, XK = E[keep], X[xrow[keep]]
+    return (EK.T @ XK, XK.sum(axis=0), EK.sum(axis=0), (EK * EK).sum(axis=0)), int(keep.sum())
+
+
+@pytest.mark.parametrize('G', [70, 130])
+@pytest.mark.parametrize('N', WIDE_N)
+def test_wide_integer_inputs_are_bit_exact_in_every_form_and_on_a_rerun(eng, N, G):
+    """Every partial sum is an integer far below 2^53 (at most 2200 x 9 x 3), so float64 numpy is exact in any order."""
+    E, X, xrow = wide_case(N, G, integer=True)
+    want, m = _integer_want(E, X, xrow)
+    eng.upload_x(X)
+    for form in FORMS:
+        eng.ensure_expression(as_form(E, form))
+        out = eng.expr_cross(xrow=xrow)
+        assert out[4] == m and out[0].shape == (G, N) and out[1].shape == (N,)
+        for name, a, b in zip(('W', 'rho', 'sx', 'sxx'), out[:4], want):
+            assert np.array_equal(a, b), (form, name)
+        eng._cross_memo = None
+        again = eng.expr_cross(xrow=xrow)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(out[:4], again[:4])) and again[4] == m, form
+
+
+@pytest.mark.parametrize('N', [65, 200, 1024])
+def test_wide_real_inputs_against_longdouble(eng, N):
+    G = 70
+    E, X, xrow = wide_case(N, G, integer=False)
+    keep = xrow >= 0
+    ref = reference_sums(E[keep], X[xrow[keep]])                     # once: the four forms hold the same float32 values
+    eng.upload_x(X)
+    outs = {}
+    for form in FORMS:
+        Ef = as_form(E, form)
+        assert np.array_equal(np.asarray(Ef.todense()) if sp.issparse(Ef) else Ef.astype(np.float64), E)
+        eng.ensure_expression(Ef)
+        outs[form] = eng.expr_cross(xrow=xrow)
+        assert outs[form][4] == int(keep.sum())
+        check_against('wide N=%d G=%d %s' % (N, G, form), ref, outs[form][4], outs[form])
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(outs['csr'][:4], outs['csc'][:4]))
+
+
+# ------------------------------------------------------------------ NaN and Inf stay where they are
+@pytest.mark.parametrize('form', ['dense-f32', 'dense-f64', 'csr', 'csc'])
+@pytest.mark.parametrize('N', [33, 200])
+def test_nan_and_inf_touch_only_their_own_gene(eng, N, form):
+    G = 70
+    E, X, xrow = wide_case(N, G, integer=True, seed=7)
+    took, left = np.flatnonzero(xrow >= 0), np.flatnonzero(xrow < 0)
+    eng.upload_x(X)
+
+    def run(M):
+        eng.ensure_expression(as_form(M, form))
+        return eng.expr_cross(xrow=xrow)
+    clean = run(E)
+    want, m = _integer_want(E, X, xrow)
+    assert all(np.array_equal(a, b) for a, b in zip(clean[:4], want))
+    # in cells that take part: the first, one in the second chunk of gene 0's list, the last; the genes 0 (three chunks), 9 and
+    # 64 (the second gene block of the dense kernel)
+    hit = {0: (took[len(took) // 2], np.nan), 9: (took[0], np.inf), 64: (took[-1], -np.inf)}
+    assert took[len(took) // 2] > 1024
+    D = E.copy()
+    for g, (cell, v) in hit.items():
+        D[cell, g] = v
+    got = run(D)
+    bad = np.zeros(G, dtype=bool)
+    bad[list(hit)] = True
+    assert got[4] == m and got[1].tobytes() == clean[1].tobytes()                     # rho
+    for a, b in zip((got[0], got[2], got[3]), (clean[0], clean[2], clean[3])):
+        assert not np.isfinite(a[bad]).any()
+        assert a[~bad].tobytes() == b[~bad].tobytes()
+    assert np.isnan(got[2][0]) and got[2][9] == np.inf and got[2][64] == -np.inf and got[3][64] == np.inf
+    # in cells without a row in X: never read into a sum
+    D = E.copy()
+    D[left[0], 0], D[left[len(left) // 2], 9], D[left[-1], 64], D[left[1], 1] = np.nan, np.inf, -np.inf, np.nan
+    got = run(D)
+    assert got[4] == m and all(a.tobytes() == b.tobytes() for a, b in zip(got[:4], clean[:4]))
+
+
+# ------------------------------------------------------------------ more than one gene tile
+def test_second_gene_tile_of_the_gene_major_cross(eng):
+    """33 100 genes of one chunk each against 1024 samples: xc_sparse goes over the genes in two tiles (the first full to its
+    last chunk, an empty gene closing it; tests/test_expr_tiles_host.py asserts that).  Integer-valued, against
+    scipy.sparse @ dense in float64, bit for bit.  W takes 271 MB on each side."""
+    from test_expr_tiles_host import cross_tile_case, assert_cross_tile_case, cross_reference
+    E, X, xrow = cross_tile_case()
+    assert_cross_tile_case(E)
+    want = cross_reference(E, X, xrow)
+    eng.upload_x(X)
+    eng.ensure_expression(E)
+    assert eng.expression_shape()['format'] == 'gene-major'
+    got = eng.expr_cross(xrow=xrow)
+    eng.drop_expression()
+    assert got[4] == want[4]
+    for name, a, b in zip(('W', 'rho', 'sx', 'sxx'), got[:4], want[:4]):
+        assert np.array_equal(a, b), name
+
+
+# ------------------------------------------------------------------ k_xc_check and k_xc_rho beyond one thread per cell
+LONG_CELLS = 1100000               # k_xc_check: 4096 blocks x 256 threads = 1 048 576 cells before the grid-stride loop starts
+LONG_GRID = 4096 * 256
+
+
+def long_case():
+    """(E, X, xrow, took): 1.1M cells x 3 genes CSC with about 5000 integer entries, a third of them in cells that take part;
+    X 500 x 33; xrow -1 but for 500 cells spread over the whole range (the first, the last, 120 beyond cell 1 048 576)."""
+    if 'long' not in _cases:
+        rs = np.random.RandomState(77)
+        n = LONG_CELLS
+        inner = rs.choice(np.arange(1, LONG_GRID), 379, replace=False)
+        outer = rs.choice(np.arange(LONG_GRID, n - 1), 119, replace=False)
+        took = np.sort(np.r_[0, inner, outer, n - 1])
+        xrow = np.full(n, -1, dtype=np.int64)
+        xrow[took] = rs.permutation(500)
+        X = rs.randint(-3, 4, (500, 33)).astype(np.float64)
+        cols = []
+        for g in range(3):
+            cells = np.unique(np.r_[rs.choice(took, 300, replace=False), rs.randint(0, n, 1400)])
+            cols.append(sp.csc_matrix((rs.randint(1, 10, len(cells)).astype(np.float64), (cells, np.zeros(len(cells), dtype=int))),
+                                      shape=(n, 1)))
+        E = sp.hstack(cols, format='csc')
+        assert len(took) == 500 and (took >= LONG_GRID).sum() >= 100 and 4500 < E.nnz < 5500
+        _cases['long'] = (E, X, xrow, took)
+    return _cases['long']
+
+
+def test_long_cell_axis_valid_map(eng):
+    E, X, xrow, took = long_case()
+    EK, XK = E.tocsr()[took], X[xrow[took]]
+    want = (np.asarray(EK.T @ XK), XK.sum(axis=0), np.asarray(EK.sum(axis=0)).ravel(), np.asarray(EK.multiply(EK).sum(axis=0)).ravel())
+    assert np.abs(want[0]).sum() > 0
+    eng.upload_x(X)
+    one = np.ascontiguousarray(E[:, [0]].toarray(), dtype=np.float32)           # dense, one gene: 4.4 MB, 2045 slabs of 538 cells
+    for tag, M, sel in (('csc', E, slice(None)), ('dense-f32 one gene', one, slice(0, 1))):
+        eng.ensure_expression(M)
+        got = eng.expr_cross(xrow=xrow)
+        assert got[4] == 500, tag
+        assert np.array_equal(got[0], want[0][sel]) and np.array_equal(got[1], want[1]), tag
+        assert np.array_equal(got[2], want[2][sel]) and np.array_equal(got[3], want[3][sel]), tag
+
+
+def test_long_cell_axis_refusals(eng):
+    """The verdicts of k_xc_check where a cell is reached by the grid-stride loop: refused before anything is written."""
+    E, X, xrow, took = long_case()
+    eng.upload_x(X)
+    eng.ensure_expression(E)
+    n = LONG_CELLS
+    low, high = took[took < LONG_GRID][5], took[took >= LONG_GRID][5]
+    free = np.flatnonzero(xrow[n - 1000:] < 0)[[3, -3]] + n - 1000                 # two cells of the last 1000 without a row
+    cases = {'twice': (high, xrow[low], 'two cells name the same row of X'),
+             'too large': (free[0], 500, 'an xrow lies outside'),
+             'far too large': (free[1], 2 ** 40, 'an xrow lies outside'),
+             'below -1': (free[1], -2, 'an xrow lies outside')}
+    for name, (i, v, msg) in cases.items():
+        bad = xrow.copy()
+        bad[i] = v
+        assert i >= LONG_GRID, name
+        rc, bufs, m = _raw_cross(eng, bad, 3, 33)
+        assert rc == -1, name                                          # CNA_EINVAL
+        assert msg in eng.lib.cna_last_error().decode(), name
+        assert all((b == 7.5).all() for b in bufs) and m == -5, name
+    rc, bufs, m = _raw_cross(eng, xrow, 3, 33)                         # the map itself passes, through the same entry
+    assert rc == 0 and m == 500
+
+
+# ------------------------------------------------------------------ end to end at a wide sample axis
+@pytest.mark.parametrize('form', ['dense-f32', 'csr'])
+def test_end_to_end_at_130_samples(eng, form):
+    """130 samples: k_xc_sparse<T, 4> / five dense tiles (the last of 2) inside the whole call.  r against gene_corr, null_r
+    against the materialised oracle, within R_TOL (the CPU difference of the restatement at 130 samples is in
+    profiles/r10_gene_cross_wide_parity.txt)."""
+    import cna_amd as cna
+    if 'wide' not in _cases:
+        from cna_amd import synth
+        data, meta = synth.make_dataset(3000, 130, k=15, seed=130)
+        _cases['wide'] = (data, meta['y'])
+    data, y = _cases['wide']
+    E = expression(3000, 70, seed=131).astype(np.float32).astype(np.float64)
+    d = type(data)(data.obs[['id']].copy(), data.obsp['connectivities'], X=as_form(E, form))
+    call = dict(nsteps=3, Nnull=50, seed=9)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        frame, null_r = cna.tl.gene_test(d, y, 'id', return_null=True, engine=eng, **call)
+        rc = cna.tl.gene_corr(d, 'coef', engine=eng)['coef'].values
+    assert null_r.shape == (70, 50) and eng.expr_cross()[0].shape == (70, 130)
+    want, kept_ref = _oracle_null(d, y, None, None, E, 50, **call)
+    assert np.array_equal(kept_ref, np.isfinite(d.obs['coef'].values))
+    ok = np.arange(70) != 1
+    assert np.isnan(frame['r'].values[1]) and np.isfinite(frame.values[ok]).all()
+    d_r = float(np.max(np.abs(frame['r'].values[ok] - rc[ok])))
+    d_null = float(np.max(np.abs(null_r[ok] - want[ok])))
+    _note('130 samples %s: max |r - gene_corr|' % form, d_r)
+    _note('130 samples %s: max |null_r - materialised oracle|' % form, d_null)
+    assert d_r <= R_TOL and d_null <= R_TOL, (d_r, d_null, R_TOL)
