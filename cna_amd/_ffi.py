@@ -142,6 +142,8 @@ SIGNATURES = {
     'cna_expr_to_bins': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'cna_expr_cross': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int64)]),
+    'cna_coef_strata': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
+                                  C.c_double] + [C.c_void_p] * 10),
     'cna_x_generation': (C.c_int, [c_ctx, C.POINTER(C.c_int64)]),
 }
 

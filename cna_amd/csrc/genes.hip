@@ -62,10 +62,7 @@ namespace {
 constexpr int GC_MAXQ = 16;
 constexpr int KS_LD = 8;   // doubles per key in the key statistics block: n, mean, sum vc^2, sum vc, min, max
 
-struct Buf {
-  void* p = nullptr;
-  int64_t cap = 0;
-};
+using Buf = DevBuf;
 
 struct ExprState {
   hipStream_t st = nullptr;
@@ -89,24 +86,8 @@ struct ExprState {
 
 inline ExprState* state_of(cna_ctx* c) { return static_cast<ExprState*>(c->expr); }
 
-int buf_free(cna_ctx* c, Buf& b) {
-  if (b.p) dev_free(c, b.p, (size_t)b.cap);
-  b.p = nullptr;
-  b.cap = 0;
-  return 0;
-}
-
-int buf_need(cna_ctx* c, ExprState* s, Buf& b, int64_t bytes) {
-  if (b.p && b.cap >= bytes) return 0;
-  if (b.p) {
-    HIP_TRY(hipStreamSynchronize(s->st));
-    buf_free(c, b);
-  }
-  if (bytes < 256) bytes = 256;
-  CNA_TRY(dev_alloc(c, &b.p, (size_t)bytes));
-  b.cap = bytes;
-  return 0;
-}
+int buf_free(cna_ctx* c, Buf& b) { return devbuf_free(c, b); }
+int buf_need(cna_ctx* c, ExprState* s, Buf& b, int64_t bytes) { return devbuf_need(c, s->st, b, bytes); }
 
 void release_matrix(cna_ctx* c, ExprState* s) {
   (void)hipStreamSynchronize(s->st);
@@ -1243,10 +1224,41 @@ int xc_sparse(cna_ctx* c, ExprState* s, const double* Xw, int ldx, int Nx, doubl
 
 }  // namespace
 
+int devbuf_free(cna_ctx* c, DevBuf& b) {
+  if (b.p) dev_free(c, b.p, (size_t)b.cap);
+  b.p = nullptr;
+  b.cap = 0;
+  return 0;
+}
+
+int devbuf_need(cna_ctx* c, hipStream_t st, DevBuf& b, int64_t bytes) {
+  if (b.p && b.cap >= bytes) return 0;
+  if (b.p) {
+    HIP_TRY(hipStreamSynchronize(st));
+    devbuf_free(c, b);
+  }
+  if (bytes < 256) bytes = 256;
+  CNA_TRY(dev_alloc(c, &b.p, (size_t)bytes));
+  b.cap = bytes;
+  return 0;
+}
+
+void launch_block_scan(hipStream_t st, unsigned int* cnt, int64_t G, int B, int64_t* total) {
+  hipLaunchKernelGGL(k_tr_scan, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, cnt, G, B, total);
+}
+
+int expr_stream(cna_ctx* c, hipStream_t* st) {
+  ExprState* s = nullptr;
+  CNA_TRY(get_state(c, &s));
+  *st = s->st;
+  return 0;
+}
+
 void expr_destroy(cna_ctx* c) {
   ExprState* s = state_of(c);
   if (!s) return;
   release_matrix(c, s);
+  strata_release(c, s->st);
   if (s->st) (void)hipStreamDestroy(s->st);
   if (s->x_ready) (void)hipEventDestroy(s->x_ready);
   delete s;
@@ -1257,7 +1269,10 @@ extern "C" {
 
 int cna_expr_drop(cna_ctx* c) {
   CHECK_CTX(c);
-  if (state_of(c)) release_matrix(c, state_of(c));
+  if (state_of(c)) {
+    release_matrix(c, state_of(c));
+    strata_release(c, state_of(c)->st);
+  }
   return 0;
 }
 

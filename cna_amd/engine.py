@@ -1241,6 +1241,31 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_expr_to_bins(self.h, ptr(codes), n_bins, int(what), ptr(sums), ptr(counts)), 'cna_expr_to_bins')
         return sums, counts
 
+    BW_KINDS = ('scott', 'silverman', 'constant')
+
+    def coef_strata(self, v, fdr, codes, n_bins, fdr_thresh, points, bw_kind='scott', bw_value=0.0):
+        """Per-bin statistics and kernel densities of a per-cell column (cna_coef_strata): `v` float64 per cell in the
+        caller's order (NaN / inf = no value), `fdr` the same or None, `codes` int32 per cell, -1 = cell left out;
+        `bw_kind` one of 'scott', 'silverman', 'constant' (`bw_value` is then the bandwidth factor).  Returns a dict:
+        n, n_kept, n_pos, n_neg int64[n_bins]; mean, ssd, min, median, max float64[n_bins]; vals float64[n_bins, points].
+        Needs no graph and no resident expression matrix; `drop_expression` frees its device buffers."""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if fdr is not None:
+            fdr = np.ascontiguousarray(fdr, dtype=np.float64)
+        if v.ndim != 1 or codes.shape != v.shape or (fdr is not None and fdr.shape != v.shape):
+            raise ValueError('coef_strata: v, fdr and codes must be 1-D and of one length')
+        n_bins, points = int(n_bins), int(points)
+        nb, npts = max(n_bins, 0), max(points, 0)
+        out = {k: np.empty(nb, dtype=np.int64) for k in ('n', 'n_kept', 'n_pos', 'n_neg')}
+        out.update({k: np.empty(nb) for k in ('mean', 'ssd', 'min', 'median', 'max')})
+        out['vals'] = np.empty((nb, npts))
+        check(self.lib.cna_coef_strata(self.h, ptr(v), None if fdr is None else ptr(fdr), ptr(codes), v.size, n_bins, points,
+                                       self.BW_KINDS.index(bw_kind), float(bw_value), float(fdr_thresh),
+                                       *[ptr(out[k]) for k in ('n', 'n_kept', 'n_pos', 'n_neg', 'mean', 'ssd', 'min', 'median',
+                                                               'max', 'vals')]), 'cna_coef_strata')
+        return out
+
     def x_generation(self):
         """How often the library has voided the working matrix X so far (cna_x_generation: every producer of X and every
         transition above it, in place or not)."""

@@ -3,9 +3,11 @@ from ._nam import nam, svd_nam, diffuse, diffuse_stepwise
 from ._association import association
 from ._genes import gene_corr
 from ._gene_test import gene_test
+from ._strata import coef_strata
 
 __all__ = [
     'association',
+    'coef_strata',
     'gene_corr',
     'gene_test',
     'nam',

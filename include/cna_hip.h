@@ -595,7 +595,8 @@ int  cna_expr_upload_dense(cna_ctx* ctx, const void* x, int64_t n_cells, int64_t
 int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indices, const void* data, int64_t n_cells,
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
- * work buffers of cna_gene_corr: cna_ctx_device_bytes returns to what it was before the upload. */
+ * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross and cna_coef_strata: cna_ctx_device_bytes returns to what
+ * it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -629,6 +630,38 @@ int  cna_gene_corr(cna_ctx* ctx, const double* V, int q, double* r_out);
  * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL: n_bins or what out of range, or a code outside
  * [-1, n_bins) -- found on the device before any sum is formed; nothing is written then. */
 int  cna_expr_to_bins(cna_ctx* ctx, const int32_t* codes, int n_bins, int what, double* sums_out, int64_t* counts_out);
+
+/* ---- the neighbourhood coefficient by cluster (csrc/strata.hip) ------------------------------ */
+/* The step of the reference's workflow between cna.tl.association and the per-gene correlations (demo/demo.ipynb):
+ *     sc.tl.leiden(d); cna.pl.violinplot(d, 'leiden', key='coef')
+ * (plotting/_strat.py:21-29 hands data.obs[key] of every level to Axes.violinplot, i.e. to matplotlib.cbook.violin_stats
+ * with mlab.GaussianKDE) as numbers: per bin the counts, the moments, the exact median and the kernel density on the grid
+ * that gets drawn, plus the cells that pass the FDR with either sign (plotting/_umap.py:10).
+ *   v[i]      the coefficient of cell i (CALLER's cell order; NaN / inf = the cell has none), n_cells in [1, 2^31)
+ *   fdr[i]    its FDR, or fdr = NULL (n_pos_out / n_neg_out are then 0)
+ *   codes[i]  its bin, -1 for a cell that is left out; 1 <= n_bins <= 1024
+ * A cell is KEPT when its code is >= 0 and v[i] is finite.  Per bin b:
+ *   n_out = cells with that code, n_kept_out = kept cells, n_pos_out / n_neg_out = kept cells with fdr[i] <= fdr_thresh (a
+ *   NaN fdr fails) and v > 0 / v < 0; mean_out, ssd_out = sum (v - mean)^2 (two passes), min_out, median_out (np.median:
+ *   both middle order statistics by an exact radix select, (a + b) / 2), max_out over the kept cells -- NaN for a bin that
+ *   keeps none (ssd 0 for one that keeps one).
+ *   vals_out[b * points + j], 1 <= points <= 1024: the density at x_j = min + j * step, step = (max - min) / (points - 1),
+ *   the last point max itself (np.linspace(min, max, points), which the caller forms from min_out / max_out).  All kept values
+ *   equal (min == max, decided exactly; this includes a single one): Axes.violinplot's fallback (x_j == value) = 1.
+ *   Otherwise mlab.GaussianKDE in its own order: var = ssd / (m - 1), f the bandwidth factor, inv = (1 / var) / f^2,
+ *   vals = sum_i exp(-(d * (inv * d)) / 2) / (sqrt(2 pi var f^2) * m), d = v_i - x_j; bw_kind 0: f = m^-0.2 (Scott),
+ *   1: f = (3 m / 4)^-0.2 (Silverman), 2: f = bw_value > 0.  A bin that keeps no cell gives 0.  float64 exp throughout.
+ * Sums are float64 in a fixed order (the kept values of a bin in cell order, cut into chunks whose partials are added in
+ * chunk order; no floating-point atomics): two runs give the same bits.
+ * Like the expression entry points it depends on nothing else the context holds and nothing depends on it: no graph and no
+ * resident expression matrix are needed, and it may be called between cna_null_local_launch and cna_null_local_fetch.  It
+ * runs on the expression stream with grow-only buffers of its own, freed by cna_expr_drop (and with the context).
+ * CNA_EINVAL, with nothing written: a parameter out of range, or a code outside [-1, n_bins) -- found on the device before
+ * any sum is formed. */
+int  cna_coef_strata(cna_ctx* ctx, const double* v, const double* fdr, const int32_t* codes, int64_t n_cells, int n_bins,
+                     int points, int bw_kind, double bw_value, double fdr_thresh, int64_t* n_out, int64_t* n_kept_out,
+                     int64_t* n_pos_out, int64_t* n_neg_out, double* mean_out, double* ssd_out, double* min_out,
+                     double* median_out, double* max_out, double* vals_out);
 
 /* ---- the expression matrix against the working matrix (csrc/genes.hip) ------------------------ */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
