@@ -307,13 +307,11 @@ struct cna_ctx {
   void* gram_tiles_ptr = nullptr;
   int64_t gram_tiles_cap = 0;
 
-  // ---- resident expression matrix and the work buffers of cna_gene_corr (genes.hip owns all of it: caller's cell order,
-  // a stream of its own; derived from nothing above, so none of the transitions of c_api.hip concerns it.  cna_expr_cross
-  // reads X from there, keeps nothing derived from it and returns only once its stream has drained)
+  // ---- the expression side (expr.h: ExprState): the resident expression matrix, a stream of its own and the work buffers of
+  // cna_gene_corr, cna_expr_to_bins, cna_expr_cross and cna_coef_strata, all in the caller's cell order; derived from nothing
+  // above, so none of the transitions of c_api.hip concerns it.  cna_expr_cross reads X from there, keeps nothing derived
+  // from it and returns only once its stream has drained
   void* expr = nullptr;
-  // ---- work buffers of cna_coef_strata (strata.hip owns them: three per-cell columns in the caller's order on the
-  // expression stream; derived from nothing above and nothing is derived from them)
-  void* strata = nullptr;
 
   // ---- profiling
   bool prof = false;
@@ -383,21 +381,8 @@ int x_ld(int Nx);   // c_api.hip: leading dimension of a working matrix with Nx 
 int null_local_prepare(cna_ctx* c, int P, const double* edges, int T, int want_tails, const double* thr);
 int null_local_go(cna_ctx* c, int col0);
 
-// genes.hip: frees the resident expression matrix and its state (cna_ctx_destroy)
+// genes.hip: frees the resident expression matrix and the state of the expression side (cna_ctx_destroy)
 void expr_destroy(cna_ctx* c);
-// genes.hip: the expression stream (created with the expression state on first use)
-int expr_stream(cna_ctx* c, hipStream_t* st);
-// genes.hip: a grow-only device buffer of the expression stream's users (contents discarded when it grows, after `st` has
-// drained), and the scan of a counting sort: cnt[b][g] (B blocks x G) -> the count in the blocks before b; total[g]
-struct DevBuf {
-  void* p = nullptr;
-  int64_t cap = 0;
-};
-int devbuf_need(cna_ctx* c, hipStream_t st, DevBuf& b, int64_t bytes);
-int devbuf_free(cna_ctx* c, DevBuf& b);
-void launch_block_scan(hipStream_t st, unsigned int* cnt, int64_t G, int B, int64_t* total);
-// strata.hip: frees the work buffers of cna_coef_strata once `st` has drained (cna_expr_drop, cna_ctx_destroy)
-void strata_release(cna_ctx* c, hipStream_t st);
 
 // ---- collectives (comm.hip)
 inline bool comm_active(const cna_ctx* c) { return c->comm != nullptr || c->shm != nullptr; }

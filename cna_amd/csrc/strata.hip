@@ -5,13 +5,11 @@
 // on the grid that Axes.violinplot draws (matplotlib.cbook.violin_stats with mlab.GaussianKDE), cna_coef_strata.
 //
 // Nothing here reads or writes the state of c_api.hip or the resident expression matrix: the three per-cell columns are in
-// the CALLER's cell order, the buffers are this file's own (cna_ctx::strata), the stream is the expression stream.
+// the CALLER's cell order, the buffers are this entry's own (StrataWork), the stream is the expression stream.
 //
-//   k_st_count      checks every code against [-1, n_bins); per block of cells and bin: the kept cells (code >= 0, finite
+//   sort (expr.h)   checks every code against [-1, n_bins); per block of cells and bin: the kept cells (code >= 0, finite
 //                   value) for the scan, and the bin's cells / kept cells passing the FDR with v > 0 / v < 0 (integer
-//                   atomics, LDS then global); the transpose's scan (genes.hip) turns the per-block kept counts into offsets
-//   k_st_fill       the kept values, bin after bin, ascending in the cell index inside a bin whatever the scheduling: a wave
-//                   takes 64 cells at a time in order and ranks equal codes by lane
+//                   atomics, LDS then global); then the kept values, bin after bin, ascending in the cell index inside a bin
 //   k_st_mom1/2     per chunk (ST_CHUNK values of one bin's segment): sum, min, max; then sum (v - mean)^2.  k_st_fold1/2
 //                   add the partials of a bin in chunk order and derive the bandwidth, the norm and the grid step
 //   k_st_hist       one pass of the exact radix select, every bin at once: histogram [bin][rank][256] of the 8-bit digit at
@@ -23,17 +21,14 @@
 //   k_st_finish     adds the partials of a (bin, point) in chunk order and divides by the norm; the all-equal fallback
 //
 // Sums take a fixed order (no floating-point atomics): two runs on one input give the same bits.
-#include "common.h"
-#include <algorithm>
+#include "expr.h"
 #include <cmath>
 #include <cstring>
-#include <vector>
 
 namespace {
 
 constexpr int ST_MAX_BINS = 1024;
 constexpr int ST_MAX_POINTS = 1024;
-constexpr int ST_MAX_BLOCKS = 1024;               // blocks of cells of the counting sort
 // Values of one bin that one wave of k_st_density takes.  With the software exp the kernel takes 42 VGPRs at two points
 // per lane (72 at eight, 112 at sixteen: 8 / 7 / 4 waves per SIMD), so latency is hidden by waves, not by a long chunk:
 // 512 values leave 2M cells ~4000 waves, four per SIMD of the 256 CUs, stage 4 KB of LDS per wave, and keep the partials
@@ -41,19 +36,34 @@ constexpr int ST_MAX_BLOCKS = 1024;               // blocks of cells of the coun
 constexpr int64_t ST_CHUNK = 512;
 constexpr int BS_LD = 8;   // doubles per bin: mean, ssd, min, median, max, grid step, inv / 2, norm
 
-using Buf = DevBuf;
-
-struct StrataState {
-  // the three columns; per-block kept counts -> offsets; [kept | n | pos | neg] x bins; verdict word; the kept values by bin
-  Buf v, fdr, code, cnt, tot, flag, seg;
-  // [bptr | first chunk of every bin | {bin, lo, hi} of every chunk]; per-chunk partials; per-bin block; select state; digit
-  // histograms; density partials; the densities
-  Buf table, mom, bin, sel, hist, part, vals;
+// the sort's policy: a cell with a code >= 0 is kept when its value is finite, what is stored is the value; tallies 1 to 3:
+// the bin's cells, its kept cells passing the FDR with v > 0, with v < 0
+struct KeptValues {
+  static constexpr int MAX_BINS = ST_MAX_BINS, TALLIES = 4;
+  using payload = double;
+  const double* v;
+  const double* fdr;               // may be null
+  double thresh;
+  __device__ double load(int64_t i) const { return v[i]; }
+  __device__ bool keep(double x) const { return finite_d(x); }
+  __device__ __forceinline__ void tally(unsigned int (*h)[MAX_BINS], int32_t cd, int64_t i, double x, bool kept) const {
+    atomicAdd(&h[1][cd], 1u);
+    if (kept && fdr && fdr[i] <= thresh) {          // a NaN fdr fails the test
+      if (x > 0.0) atomicAdd(&h[2][cd], 1u);
+      else if (x < 0.0) atomicAdd(&h[3][cd], 1u);
+    }
+  }
 };
 
-inline StrataState* state_of(cna_ctx* c) { return static_cast<StrataState*>(c->strata); }
-
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.79769313486231570815e308; }
+struct StrataWork : BufSet {
+  // the value and fdr columns; the sort with the codes, the totals [kept | n | pos | neg] x bins and the chunk table
+  // [bptr | first chunk of every bin | {bin, lo, hi} of every chunk]; the kept values by bin
+  Buf v{*this}, fdr{*this};
+  CodeSort sort{*this};
+  Buf seg{*this};
+  // per-chunk partials; per-bin block; select state; digit histograms; density partials; the densities
+  Buf mom{*this}, bin{*this}, sel{*this}, hist{*this}, part{*this}, vals{*this};
+};
 
 __device__ __forceinline__ unsigned long long order_key(double x) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(x);
@@ -71,82 +81,7 @@ __device__ __forceinline__ double grid_point(double mn, double mx, double step, 
   return t + mn;
 }
 
-// ------------------------------------------------------------------ counting and compaction
-// block b: cnt[b][bin] = kept cells of [r0, r1) with that code; tot[1..3][bin] += cells, kept cells passing the FDR with
-// v > 0, with v < 0; *bad |= 1 for a code outside [-1, n_bins)
-__global__ __launch_bounds__(256) void k_st_count(const double* __restrict__ v, const double* __restrict__ fdr,
-                                                  const int32_t* __restrict__ codes, int64_t n, int n_bins, int64_t rows_per_block,
-                                                  double thresh, unsigned int* __restrict__ cnt,
-                                                  unsigned long long* __restrict__ tot, int* __restrict__ bad) {
-  __shared__ unsigned int h[4][ST_MAX_BINS];
-  for (int b = threadIdx.x; b < n_bins; b += blockDim.x) h[0][b] = h[1][b] = h[2][b] = h[3][b] = 0;
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
-  for (int64_t i = r0 + threadIdx.x; i < r1; i += blockDim.x) {
-    const int32_t cd = codes[i];
-    if (cd < -1 || cd >= n_bins) {
-      atomicOr(bad, 1);
-    } else if (cd >= 0) {
-      atomicAdd(&h[1][cd], 1u);
-      const double x = v[i];
-      if (finite_d(x)) {
-        atomicAdd(&h[0][cd], 1u);
-        if (fdr && fdr[i] <= thresh) {          // a NaN fdr fails the test
-          if (x > 0.0) atomicAdd(&h[2][cd], 1u);
-          else if (x < 0.0) atomicAdd(&h[3][cd], 1u);
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b < n_bins; b += blockDim.x) {
-    cnt[(int64_t)blockIdx.x * n_bins + b] = h[0][b];
-    for (int k = 1; k < 4; ++k)
-      if (h[k][b]) atomicAdd(&tot[(int64_t)k * n_bins + b], (unsigned long long)h[k][b]);
-  }
-}
-
-// one wave per block of cells; cur[bin] = kept cells of the bin in the blocks before this one plus those already placed.
-// Among the 64 cells of a batch equal codes are ranked by lane, so a bin's values keep the order of the cells.
-__global__ __launch_bounds__(64) void k_st_fill(const double* __restrict__ v, const int32_t* __restrict__ codes, int64_t n, int n_bins,
-                                                int64_t rows_per_block, const unsigned int* __restrict__ cnt,
-                                                const int64_t* __restrict__ bptr, double* __restrict__ seg) {
-  __shared__ unsigned int cur[ST_MAX_BINS];
-  const int lane = threadIdx.x;
-  for (int b = lane; b < n_bins; b += 64) cur[b] = cnt[(int64_t)blockIdx.x * n_bins + b];
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
-  for (int64_t base = r0; base < r1; base += 64) {
-    const int64_t i = base + lane;
-    const double x = i < r1 ? v[i] : 0.0;
-    int32_t cd = i < r1 ? codes[i] : -1;
-    if (cd < 0 || cd >= n_bins || !finite_d(x)) cd = -1;
-    unsigned int rank = 0;
-    bool last = true;
-    for (int j = 0; j < 64; ++j) {
-      const bool same = __shfl(cd, j, 64) == cd;
-      rank += (same && j < lane) ? 1u : 0u;
-      last = last && !(same && j > lane);
-    }
-    if (cd >= 0) seg[bptr[cd] + (int64_t)(cur[cd] + rank)] = x;
-    __syncthreads();
-    if (cd >= 0 && last) cur[cd] += rank + 1u;
-    __syncthreads();
-  }
-}
-
 // ------------------------------------------------------------------ moments
-__device__ __forceinline__ double wave_min_d(double v) {
-  for (int w = 32; w > 0; w >>= 1) v = fmin(v, __shfl_xor(v, w, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max_any(double v) {
-  for (int w = 32; w > 0; w >>= 1) v = fmax(v, __shfl_xor(v, w, 64));
-  return v;
-}
-
 // chunk table: tab[3 ch] = bin, tab[3 ch + 1], tab[3 ch + 2] = the chunk's span of seg (never empty, at most ST_CHUNK).
 // Lane l adds the values l, l + 64, ... of the chunk, the 64 sums are folded by wave_sum: a fixed order.
 __global__ __launch_bounds__(64) void k_st_mom1(const double* __restrict__ seg, const int64_t* __restrict__ tab, double* __restrict__ mom) {
@@ -159,8 +94,8 @@ __global__ __launch_bounds__(64) void k_st_mom1(const double* __restrict__ seg, 
     mx = fmax(mx, x);
   }
   s = wave_sum(s);
-  mn = wave_min_d(mn);
-  mx = wave_max_any(mx);
+  mn = wave_min(mn);
+  mx = wave_max(mx);
   if (threadIdx.x == 0) {
     mom[4 * ch] = s;
     mom[4 * ch + 1] = mn;
@@ -351,24 +286,7 @@ __global__ __launch_bounds__(256) void k_st_finish(const double* __restrict__ pa
   vals[t] = r;
 }
 
-template <int NP>
-void launch_density(hipStream_t st, int64_t nch, const StrataState* s, const int64_t* tab, int points) {
-  hipLaunchKernelGGL((k_st_density<NP>), dim3((unsigned)nch), dim3(64), 0, st, (const double*)s->seg.p, tab,
-                     (const double*)s->bin.p, points, (double*)s->part.p);
-}
-
 }  // namespace
-
-void strata_release(cna_ctx* c, hipStream_t st) {
-  StrataState* s = state_of(c);
-  if (!s) return;
-  if (st) (void)hipStreamSynchronize(st);
-  for (Buf* b : {&s->v, &s->fdr, &s->code, &s->cnt, &s->tot, &s->flag, &s->seg, &s->table, &s->mom, &s->bin, &s->sel, &s->hist,
-                 &s->part, &s->vals})
-    devbuf_free(c, *b);
-  delete s;
-  c->strata = nullptr;
-}
 
 extern "C" int cna_coef_strata(cna_ctx* c, const double* v, const double* fdr, const int32_t* codes, int64_t n_cells, int n_bins,
                                int points, int bw_kind, double bw_value, double fdr_thresh, int64_t* n_out, int64_t* n_kept_out,
@@ -384,70 +302,34 @@ extern "C" int cna_coef_strata(cna_ctx* c, const double* v, const double* fdr, c
   if (bw_kind < 0 || bw_kind > 2) CNA_FAIL(CNA_EINVAL, "cna_coef_strata: bw_kind is 0 (Scott), 1 (Silverman) or 2 (bw_value)");
   if (bw_kind == 2 && !(bw_value > 0.0 && bw_value <= 1.79769313486231570815e308))
     CNA_FAIL(CNA_EINVAL, "cna_coef_strata: bw_value must be a positive finite number");
-  hipStream_t st = nullptr;
-  CNA_TRY(expr_stream(c, &st));
-  if (!c->strata) c->strata = new StrataState();
-  StrataState* s = state_of(c);
+  ExprState* es = nullptr;
+  CNA_TRY(expr_get_state(c, &es));
+  hipStream_t st = es->st;
+  StrataWork* s = expr_work<StrataWork>(es, EXPR_STRATA);
   const int64_t n = n_cells;
-  const int64_t rpb = round_up64((n + ST_MAX_BLOCKS - 1) / ST_MAX_BLOCKS, 64);
-  const int64_t B = (n + rpb - 1) / rpb;
-  CNA_TRY(devbuf_need(c, st, s->v, 8 * n));
-  if (fdr) CNA_TRY(devbuf_need(c, st, s->fdr, 8 * n));
-  CNA_TRY(devbuf_need(c, st, s->code, 4 * n));
-  CNA_TRY(devbuf_need(c, st, s->cnt, 4 * B * n_bins));
-  CNA_TRY(devbuf_need(c, st, s->tot, 8 * 4 * (int64_t)n_bins));
-  CNA_TRY(devbuf_need(c, st, s->flag, 256));
+  CNA_TRY(buf_need(c, st, s->v, 8 * n));
+  if (fdr) CNA_TRY(buf_need(c, st, s->fdr, 8 * n));
   HIP_TRY(hipMemcpyAsync(s->v.p, v, (size_t)(8 * n), hipMemcpyHostToDevice, st));
   if (fdr) HIP_TRY(hipMemcpyAsync(s->fdr.p, fdr, (size_t)(8 * n), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->code.p, codes, (size_t)(4 * n), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(s->flag.p, 0, 4, st));
-  HIP_TRY(hipMemsetAsync(s->tot.p, 0, (size_t)(8 * 4 * (int64_t)n_bins), st));
-  unsigned long long* tot_dev = (unsigned long long*)s->tot.p;
-  hipLaunchKernelGGL(k_st_count, dim3((unsigned)B), dim3(256), 0, st, (const double*)s->v.p,
-                     fdr ? (const double*)s->fdr.p : (const double*)nullptr, (const int32_t*)s->code.p, n, n_bins, rpb, fdr_thresh,
-                     (unsigned int*)s->cnt.p, tot_dev, (int*)s->flag.p);
-  launch_block_scan(st, (unsigned int*)s->cnt.p, n_bins, (int)B, (int64_t*)s->tot.p);   // kept counts -> offsets, tot[0][bin]
-  HIP_TRY(hipGetLastError());
-  // the codes are judged before any sum is formed
-  int bad = 0;
-  std::vector<int64_t> tot(4 * (size_t)n_bins);
-  HIP_TRY(hipMemcpyAsync(&bad, s->flag.p, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(tot.data(), s->tot.p, 8 * tot.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (bad) CNA_FAIL(CNA_EINVAL, "cna_coef_strata: a code lies outside [-1, n_bins)");
-
-  // [bptr | first chunk of every bin | {bin, lo, hi} of every chunk]
-  const size_t nb1 = (size_t)n_bins + 1;
-  std::vector<int64_t> table(2 * nb1, 0);
-  for (int b = 0; b < n_bins; ++b) {
-    const int64_t lo = table[(size_t)b], hi = lo + tot[(size_t)b];
-    table[(size_t)b + 1] = hi;
-    table[nb1 + (size_t)b] = ((int64_t)table.size() - 2 * (int64_t)nb1) / 3;
-    for (int64_t e = lo; e < hi; e += ST_CHUNK) {
-      table.push_back(b);
-      table.push_back(e);
-      table.push_back(std::min(e + ST_CHUNK, hi));
-    }
-  }
-  const int64_t nch = ((int64_t)table.size() - 2 * (int64_t)nb1) / 3;
-  table[nb1 + (size_t)n_bins] = nch;
-  const int64_t kept_all = table[(size_t)n_bins];
-  CNA_TRY(devbuf_need(c, st, s->seg, 8 * std::max<int64_t>(1, kept_all)));
-  CNA_TRY(devbuf_need(c, st, s->table, 8 * (int64_t)table.size()));
-  CNA_TRY(devbuf_need(c, st, s->mom, 8 * 4 * std::max<int64_t>(1, nch)));
-  CNA_TRY(devbuf_need(c, st, s->bin, 8 * BS_LD * (int64_t)n_bins));
-  CNA_TRY(devbuf_need(c, st, s->sel, (int64_t)sizeof(SelState) * n_bins));
-  CNA_TRY(devbuf_need(c, st, s->hist, 4 * 512 * (int64_t)n_bins));
-  CNA_TRY(devbuf_need(c, st, s->part, 8 * std::max<int64_t>(1, nch) * points));
-  CNA_TRY(devbuf_need(c, st, s->vals, 8 * (int64_t)n_bins * points));
-  HIP_TRY(hipMemcpyAsync(s->table.p, table.data(), 8 * table.size(), hipMemcpyHostToDevice, st));
-  const int64_t* bptr = (const int64_t*)s->table.p;
-  const int64_t* first = bptr + nb1;
-  const int64_t* tab = first + nb1;
-  double* bin = (double*)s->bin.p;
+  const KeptValues kept{s->v.as<const double>(), fdr ? s->fdr.as<const double>() : nullptr, fdr_thresh};
+  CNA_TRY(sort_count(c, st, s->sort, kept, codes, n, n_bins, ST_CHUNK, 3, "cna_coef_strata: a code lies outside [-1, n_bins)"));
+  const std::vector<int64_t>& tot = s->sort.tot_h;
+  const int64_t nch = s->sort.nch;
+  int64_t kept_all = 0;
+  for (int b = 0; b < n_bins; ++b) kept_all += tot[(size_t)b];
+  CNA_TRY(buf_need(c, st, s->seg, 8 * std::max<int64_t>(1, kept_all)));
+  CNA_TRY(buf_need(c, st, s->mom, 8 * 4 * std::max<int64_t>(1, nch)));
+  CNA_TRY(buf_need(c, st, s->bin, 8 * BS_LD * (int64_t)n_bins));
+  CNA_TRY(buf_need(c, st, s->sel, (int64_t)sizeof(SelState) * n_bins));
+  CNA_TRY(buf_need(c, st, s->hist, 4 * 512 * (int64_t)n_bins));
+  CNA_TRY(buf_need(c, st, s->part, 8 * std::max<int64_t>(1, nch) * points));
+  CNA_TRY(buf_need(c, st, s->vals, 8 * (int64_t)n_bins * points));
+  const unsigned long long* tot_dev = s->sort.totals();
+  const int64_t* first = s->sort.first();
+  const int64_t* tab = s->sort.chunks();
+  double* bin = s->bin.as<double>();
   const unsigned bin_blocks = (unsigned)((n_bins + 255) / 256);
-  hipLaunchKernelGGL(k_st_fill, dim3((unsigned)B), dim3(64), 0, st, (const double*)s->v.p, (const int32_t*)s->code.p, n, n_bins, rpb,
-                     (const unsigned int*)s->cnt.p, bptr, (double*)s->seg.p);
+  sort_fill(st, s->sort, kept, n, s->seg.as<double>());
   if (nch) hipLaunchKernelGGL(k_st_mom1, dim3((unsigned)nch), dim3(64), 0, st, (const double*)s->seg.p, tab, (double*)s->mom.p);
   hipLaunchKernelGGL(k_st_fold1, dim3(bin_blocks), dim3(256), 0, st, (const double*)s->mom.p, first, tot_dev, n_bins, bin);
   if (nch) hipLaunchKernelGGL(k_st_mom2, dim3((unsigned)nch), dim3(64), 0, st, (const double*)s->seg.p, tab, (const double*)bin,
@@ -463,25 +345,15 @@ extern "C" int cna_coef_strata(cna_ctx* c, const double* v, const double* fdr, c
       hipLaunchKernelGGL(k_st_pick, dim3((unsigned)n_bins), dim3(64), 0, st, (unsigned int*)s->hist.p, (SelState*)s->sel.p,
                          tot_dev, shift, bin);
     }
-    const int np = (points + 63) / 64;
-    if (np <= 1) launch_density<1>(st, nch, s, tab, points);
-    else if (np <= 2) launch_density<2>(st, nch, s, tab, points);
-    else if (np <= 4) launch_density<4>(st, nch, s, tab, points);
-    else if (np <= 8) launch_density<8>(st, nch, s, tab, points);
-    else launch_density<16>(st, nch, s, tab, points);
+    with_width((points + 63) / 64, [&](auto np) {
+      hipLaunchKernelGGL((k_st_density<decltype(np)::value>), dim3((unsigned)nch), dim3(64), 0, st, (const double*)s->seg.p, tab,
+                         (const double*)bin, points, (double*)s->part.p);
+    });
   }
   hipLaunchKernelGGL(k_st_finish, dim3((unsigned)(((int64_t)n_bins * points + 255) / 256)), dim3(256), 0, st,
                      (const double*)s->part.p, first, tot_dev, (const double*)bin, n_bins, points, (double*)s->vals.p);
   std::vector<double> hb((size_t)BS_LD * n_bins), hv((size_t)n_bins * points);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), bin, 8 * hb.size(), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), s->vals.p, 8 * hv.size(), hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) {
-    cna_set_error(std::string("cna_coef_strata: ") + hipGetErrorString(e));
-    return (int)e;
-  }
+  CNA_TRY(fetch_results(st, "cna_coef_strata", {{hb.data(), bin, 8 * hb.size()}, {hv.data(), s->vals.p, 8 * hv.size()}}));
   for (int b = 0; b < n_bins; ++b) {
     const double* o = hb.data() + (size_t)b * BS_LD;
     n_kept_out[b] = tot[(size_t)b];

@@ -8,7 +8,7 @@ permutation p is ``c_p = R^T z_p / N`` (_association.py:99; the observed one is 
 residualised NAM -- the working matrix X on the device -- and every cell-sized sum a correlation with ``c_p`` needs is
 linear or quadratic in ``z_p``::
 
-    sum_i x_ig c_p[i] = (W_g . z_p) / N        W   = E_K^T X   genes x samples   (cna_expr_cross, csrc/genes.hip)
+    sum_i x_ig c_p[i] = (W_g . z_p) / N        W   = E_K^T X   genes x samples   (cna_expr_cross, csrc/expr_cross.hip)
     sum_i c_p[i]      = (rho . z_p) / N        rho = column sums of X
     sum_i c_p[i]^2    = z_p^T Gamma z_p / N^2  Gamma = X^T X                     (the association's Gram matrix)
 

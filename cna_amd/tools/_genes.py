@@ -7,7 +7,7 @@ correlations to neighborhood coefficient")::
 
 which builds a (genes + 1) x (genes + 1) matrix to read one row of it, does not take a sparse ``X`` and turns all-NaN as
 soon as the QC dropped one cell.  Here the expression matrix goes to the device once (``Engine.ensure_expression``) and
-every call is one pass over it (csrc/genes.hip).  This module is the host side only: argument checks and the frame.
+every call is one pass over it (csrc/genes.hip, csrc/expr_corr.hip).  This module is the host side only: argument checks and the frame.
 """
 import numpy as np
 import pandas as pd

@@ -3,7 +3,7 @@
 ``obs_to_sample`` (reference utils/multisample.py:4-11) turns per-cell columns of ``data.obs`` into one row per sample;
 this is the same aggregation for ``data.X``, so that mean expression per sample (or per sample and cluster) sits beside
 ``y``, ``covs``, ``res.yresid`` and ``res.namresid_sampleXpc`` row for row.  The expression matrix is the one
-``cna.tl.gene_corr`` keeps resident (``Engine.ensure_expression``); a call is one pass over it (csrc/genes.hip,
+``cna.tl.gene_corr`` keeps resident (``Engine.ensure_expression``); a call is one pass over it (csrc/expr_bins.hip,
 ``cna_expr_to_bins``).  This module is the host side only: the codes, the argument checks and the frame.
 """
 import numpy as np

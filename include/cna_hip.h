@@ -570,7 +570,7 @@ int  cna_host_permute_rows(const int64_t* perm, int64_t r0, int64_t r1, const in
 int  cna_knn_graph(cna_ctx* ctx, const float* X, int64_t n, int d, int k, int64_t* indptr_out,
                    int32_t* indices_out, float* data_out, int64_t* nnz_out);
 
-/* ---- per-gene correlation to per-cell columns (csrc/genes.hip) ------------------------------ */
+/* ---- per-gene correlation to per-cell columns (csrc/genes.hip, expr_corr.hip) ----------------- */
 /* The step of the reference's workflow that follows cna.tl.association (demo/demo.ipynb, "per-gene correlations to
  * neighborhood coefficient"):
  *     d.var['corr_case'] = np.corrcoef(d.obs.male_coef.values.reshape(1,-1), d.X, rowvar=False)[0,1:]
@@ -613,7 +613,7 @@ int  cna_expr_shape(cna_ctx* ctx, int64_t* n_cells, int64_t* n_genes, int64_t* n
  * CNA_ESTATE: no expression matrix is resident. */
 int  cna_gene_corr(cna_ctx* ctx, const double* V, int q, double* r_out);
 
-/* ---- per-bin sums of the resident expression matrix (csrc/genes.hip) ------------------------- */
+/* ---- per-bin sums of the resident expression matrix (csrc/expr_bins.hip) --------------------- */
 /* The sample-level side of the reference's workflow: utils/multisample.py:4-11 (obs_to_sample) turns per-cell columns of
  * d.obs into one row per sample; this is the same aggregation for d.X, the samples x genes matrix of summed expression
  * ("pseudobulk"), over the matrix cna_expr_upload_* left on the device, dense or gene-major.  codes[i] is the bin (row of
@@ -663,7 +663,7 @@ int  cna_coef_strata(cna_ctx* ctx, const double* v, const double* fdr, const int
                      int64_t* n_pos_out, int64_t* n_neg_out, double* mean_out, double* ssd_out, double* min_out,
                      double* median_out, double* max_out, double* vals_out);
 
-/* ---- the expression matrix against the working matrix (csrc/genes.hip) ------------------------ */
+/* ---- the expression matrix against the working matrix (csrc/expr_cross.hip) ------------------- */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
  * z_p (_association.py:94-99; the observed one is _association.py:77 with z = the standardised y), the correlation of
  * gene g with c_p -- demo/demo.ipynb's "per-gene correlations to neighborhood coefficient" under the null -- needs

@@ -2,7 +2,8 @@
 
 Both entries keep the partial sums of the gene-major kernels under PB_PART_BYTES by going over the genes in tiles of whole
 genes: at most max_chunks = PB_PART_BYTES / (8 * width) chunks per tile, width = the bins of cna_expr_to_bins or the
-samples of cna_expr_cross (csrc/genes.hip: pb_sparse, xc_sparse).  A chunk is a piece of one gene's list (build_chunks):
+samples of cna_expr_cross (csrc/expr.h: gene_tiles, walked by pb_sparse of expr_bins.hip and xc_sparse of expr_cross.hip).
+A chunk is a piece of one gene's list (genes.hip: build_chunks):
 its length is nnz / 16384, held to [1024, 65536] and rounded up to a multiple of 64.
 
 This file restates those two rules in Python, builds the two inputs the GPU tests use (tests/test_gpu_expr_to_sample.py,
@@ -21,8 +22,9 @@ _built = {}
 
 
 def source_constant(name):
-    """An integer constant of csrc/genes.hip, written as `123` or as `123ll << 20`."""
-    src = open(os.path.join(ROOT, 'cna_amd', 'csrc', 'genes.hip')).read()
+    """An integer constant of the expression side (csrc/genes.hip, expr_bins.hip, expr_cross.hip), written as `123` or as
+    `123ll << 20`."""
+    src = ''.join(open(os.path.join(ROOT, 'cna_amd', 'csrc', f)).read() for f in ('genes.hip', 'expr_bins.hip', 'expr_cross.hip'))
     m = re.search(r'constexpr (?:int|int64_t) %s = (\d+)(?:ll)?(?: << (\d+))?;' % name, src)
     assert m, name
     return int(m.group(1)) << int(m.group(2) or 0)
