@@ -144,6 +144,7 @@ SIGNATURES = {
                                  C.POINTER(C.c_int64)]),
     'cna_coef_strata': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
                                   C.c_double] + [C.c_void_p] * 10),
+    'cna_gene_corr_by': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cna_x_generation': (C.c_int, [c_ctx, C.POINTER(C.c_int64)]),
 }
 

@@ -1,10 +1,11 @@
 // Private to the expression side of the library -- the resident expression matrix (genes.hip) and the entry points that
 // work on the expression stream, one file each: cna_gene_corr (expr_corr.hip), cna_expr_to_bins (expr_bins.hip),
-// cna_expr_cross (expr_cross.hip), cna_coef_strata (strata.hip).  What two of them need is here once:
+// cna_expr_cross (expr_cross.hip), cna_coef_strata (strata.hip), cna_gene_corr_by (expr_corr_by.hip).  What two of them
+// need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared
 //   ExprState       the resident matrix, the stream, and one slot of work buffers per entry point
-//   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins, value segments of
-//                   cna_coef_strata): one count kernel, one fill kernel, one host half
+//   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins and cna_gene_corr_by, value
+//                   segments of cna_coef_strata): one count kernel, one fill kernel, one host half; CellListOf
 //   gene_tiles      the walk over tiles of whole genes of the gene-major kernels
 //   with_bool / with_width, fetch_results, finite_d, wave_min / wave_max
 // Templates are instantiated where they are used; nothing here needs relocatable device code.
@@ -49,7 +50,7 @@ struct ScopedBufs : BufSet {
 };
 
 // ------------------------------------------------------------------ state (cna_ctx::expr)
-enum ExprUser { EXPR_CORR, EXPR_BINS, EXPR_CROSS, EXPR_STRATA, EXPR_USERS };
+enum ExprUser { EXPR_CORR, EXPR_BINS, EXPR_CROSS, EXPR_STRATA, EXPR_CORR_BY, EXPR_USERS };
 
 struct ExprState {
   hipStream_t st = nullptr;
@@ -278,3 +279,13 @@ void sort_fill(hipStream_t st, const CodeSort& s, const P& p, int64_t n, typenam
   hipLaunchKernelGGL((k_sort_fill<P>), dim3((unsigned)s.blocks), dim3(64), 0, st, p, s.codes(), n, s.n_bins, s.rows_per_block,
                      s.cnt.as<const unsigned int>(), s.bptr(), out);
 }
+
+// the policy of a cell list (cna_expr_to_bins, cna_gene_corr_by; BINS: the entry's own cap): every cell with a code >= 0 is
+// kept, what is stored is its index
+template <int BINS>
+struct CellListOf {
+  static constexpr int MAX_BINS = BINS, TALLIES = 1;
+  using payload = int32_t;
+  __device__ int32_t load(int64_t i) const { return (int32_t)i; }
+  __device__ bool keep(int32_t) const { return true; }
+};

@@ -21,14 +21,7 @@
 namespace {
 
 constexpr int PB_MAX_BINS = 4096;
-
-// the sort's policy: every cell with a code >= 0 is kept, what is stored is its index
-struct CellList {
-  static constexpr int MAX_BINS = PB_MAX_BINS, TALLIES = 1;
-  using payload = int32_t;
-  __device__ int32_t load(int64_t i) const { return (int32_t)i; }
-  __device__ bool keep(int32_t) const { return true; }
-};
+using CellList = CellListOf<PB_MAX_BINS>;   // the sort's policy (expr.h)
 
 // the sort with its codes and chunks of the bins; the cell list; partial sums; the sums
 struct BinsWork : BufSet {

@@ -1241,6 +1241,25 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_expr_to_bins(self.h, ptr(codes), n_bins, int(what), ptr(sums), ptr(counts)), 'cna_expr_to_bins')
         return sums, counts
 
+    def gene_corr_by(self, V, codes, n_bins, want_within=True):
+        """Pearson correlation of every gene of the resident expression matrix with every row of V (q x cells float64,
+        caller's cell order, non-finite = cell left out of that key) inside every level of `codes` (int32 per cell, -1 =
+        cell left out), and the pooled within-level correlation (cna_gene_corr_by).  Returns (r float64[q, n_bins, genes],
+        within float64[q, genes] or None, n int64[q, n_bins]: cells of the level with a finite key)."""
+        V = _f64(V)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        info = self.expression_shape()
+        if info['format'] != 'none' and (V.ndim != 2 or codes.shape != (info['n_cells'],) or V.shape[1] != info['n_cells']):
+            raise ValueError('gene_corr_by: keys %s and %d codes for %d resident cells'
+                             % (V.shape, codes.size, info['n_cells']))
+        q, n_bins = int(V.shape[0]), int(n_bins)
+        r = np.empty((q, max(n_bins, 0), info['n_genes']))
+        within = np.empty((q, info['n_genes'])) if want_within else None
+        n = np.empty((q, max(n_bins, 0)), dtype=np.int64)
+        check(self.lib.cna_gene_corr_by(self.h, ptr(V), q, ptr(codes), n_bins, ptr(r), None if within is None else ptr(within),
+                                        ptr(n)), 'cna_gene_corr_by')
+        return r, within, n
+
     BW_KINDS = ('scott', 'silverman', 'constant')
 
     def coef_strata(self, v, fdr, codes, n_bins, fdr_thresh, points, bw_kind='scott', bw_value=0.0):

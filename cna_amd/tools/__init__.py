@@ -4,11 +4,13 @@ from ._association import association
 from ._genes import gene_corr
 from ._gene_test import gene_test
 from ._strata import coef_strata
+from ._gene_strata import gene_corr_strata
 
 __all__ = [
     'association',
     'coef_strata',
     'gene_corr',
+    'gene_corr_strata',
     'gene_test',
     'nam',
     'svd_nam',

@@ -595,7 +595,7 @@ int  cna_expr_upload_dense(cna_ctx* ctx, const void* x, int64_t n_cells, int64_t
 int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indices, const void* data, int64_t n_cells,
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
- * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross and cna_coef_strata: cna_ctx_device_bytes returns to what
+ * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata and cna_gene_corr_by: cna_ctx_device_bytes returns to what
  * it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
@@ -662,6 +662,31 @@ int  cna_coef_strata(cna_ctx* ctx, const double* v, const double* fdr, const int
                      int points, int bw_kind, double bw_value, double fdr_thresh, int64_t* n_out, int64_t* n_kept_out,
                      int64_t* n_pos_out, int64_t* n_neg_out, double* mean_out, double* ssd_out, double* min_out,
                      double* median_out, double* max_out, double* vals_out);
+
+/* ---- per-gene correlations inside every level of a clustering (csrc/expr_corr_by.hip) -------- */
+/* The question after cna.pl.violinplot(d, 'leiden', key='coef') (plotting/_strat.py:21-29) shows a cluster whose violin
+ * spans both signs: which genes separate its expanded cells from its depleted ones?  The global line of demo/demo.ipynb
+ * ("per-gene correlations to neighborhood coefficient") cannot say, it is dominated by the cluster markers.  One pass over
+ * the resident matrix, the cell's level as the accumulator index:
+ *   V         q x n_cells row-major, 1 <= q <= 16, CALLER's cell order; a non-finite value leaves the cell out of that key
+ *   codes[i]  the level of cell i, -1 for a cell that is left out; 1 <= n_bins <= 1024 and q x n_bins <= 4096
+ * For key j and level L let C = the cells with code L and a finite V[j]:
+ *   n_out[j * n_bins + L] = |C|
+ *   r_out[(j * n_bins + L) * n_genes + g] = Pearson correlation of gene g with V[j] over C (implicit zeros of a sparse upload
+ *   count), by the rules of cna_gene_corr level by level: the key is centred on its mean over C before it is multiplied; NaN
+ *   where |C| < 2, where V[j] is constant on C or the gene is (minimum == maximum, decided exactly); otherwise clipped to
+ *   [-1, 1].
+ *   within_out[j * n_genes + g] (may be NULL) = the pooled within-level correlation, sum_L cov_L / sqrt(sum_L varx_L *
+ *   sum_L varv_L) with the centred sums of every level: the correlation of (x - level mean) with (v - level mean) over the
+ *   cells that have a level and a finite V[j].  A level where the gene is constant adds exactly 0 to cov and varx, one where
+ *   the key is constant exactly 0 to cov and varv; NaN when no level has the gene, or none the key, non-constant.
+ * Sums are float64 in a fixed order (the cells of a level ascending, cut into chunks whose partials are added in chunk order,
+ * the levels ascending; no floating-point atomics): two runs give the same bits.  Runs on the expression stream with
+ * grow-only buffers of its own (freed by cna_expr_drop) and changes no other state.
+ * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL, with nothing written: q or n_bins out of range, or a code
+ * outside [-1, n_bins) -- found on the device before any sum is formed. */
+int  cna_gene_corr_by(cna_ctx* ctx, const double* V, int q, const int32_t* codes, int n_bins, double* r_out,
+                      double* within_out, int64_t* n_out);
 
 /* ---- the expression matrix against the working matrix (csrc/expr_cross.hip) ------------------- */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
