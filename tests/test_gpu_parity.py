@@ -1061,19 +1061,27 @@ def test_selection_as_a_by_product_of_the_last_walk_step(eng, monkeypatch, n, N,
         np.testing.assert_allclose(a, b, rtol=1e-9, atol=1e-12)
 
 
-@pytest.mark.parametrize('n,N,K,nsteps', [(70001, 200, 4, 3), (66001, 100, 2, 3), (41000, 180, 2, 3), (30000, 200, 4, 3)])
+@pytest.mark.parametrize('n,N,K,nsteps', [(70001, 200, 4, 3), (66001, 100, 2, 3), (41000, 180, 2, 3), (30000, 200, 4, 3),
+                                          (66001, 80, 2, 3), (66001, 300, 2, 3)])
 def test_gram_under_the_walks_last_step(eng, monkeypatch, n, N, K, nsteps):
     """NAM.dot(NAM.T) (_nam.py:105) is a sum over cells, and the walk's last step writes the standardised rows one by one
     (select_tail): that step runs in K row ranges and the Gram kernel of each range follows it on a second stream, carrying
     its partial tiles from range to range (c_api.hip:ranged_last_step, mfma.hip:launch_gram_range).  Every workgroup adds
     the same slabs in the same order as the one-launch kernel, so the matrix -- and with it every result -- is the same
-    bit for bit.  The 3 x 3-block kernel (200 / 180 samples) and the strided one (100), a dense and a compressed last
-    step, a ragged last range; 30 000 cells are too few for four ranges (one launch, Gram afterwards)."""
+    bit for bit.  The 3 x 3-block kernel on 16 waves (200 / 180 samples) and on 8 (100), the tile-per-wave kernel with two
+    slabs in LDS (80: k_gram_db; the step is split only beyond 64 samples) and with one (300: k_gram, two grid.y passes),
+    a dense and a compressed last step, a ragged last range; 30 000 cells are too few for four ranges (one launch, Gram
+    afterwards)."""
     import cna_amd as cna
     from cna_amd import synth
     from cna_amd.tools import _association as A
+    from cna_amd.tools import _nam
     monkeypatch.setattr(A, '_DEFER_LAST_CELLS', 0)
     data, meta = synth.make_dataset(n, N, k=15, seed=33)
+    # (This test counts launches.  The memo of the sample ids is keyed by where the column lives: a column of the same
+    # length as the previous case's, allocated where that one was, is taken for it, the analysis starts on the old
+    # ids and starts over once the content hash has been compared -- same results, twice the launches.)
+    _nam.drop_codes_memo()
     out = {}
     monkeypatch.setattr(eng, 'reuse_nam', False)          # both runs walk
     for ranged in (True, False):
