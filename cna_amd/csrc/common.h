@@ -546,4 +546,32 @@ __device__ __forceinline__ double wave_sum(double v) {
   const double r3 = __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
   return (r0 + r1) + (r2 + r3);
 }
+// the same two over a row of 16 lanes (four cells per wave): the four DPP steps alone, every lane gets its row's result
+__device__ __forceinline__ double row16_sum(double v) {
+  v = dpp_add(v, 0);
+  v = dpp_add(v, 1);
+  v = dpp_add(v, 2);
+  return dpp_add(v, 3);
+}
+__device__ __forceinline__ double row16_max(double v) {
+  v = fmax(v, dpp_partner(v, 0));
+  v = fmax(v, dpp_partner(v, 1));
+  v = fmax(v, dpp_partner(v, 2));
+  return fmax(v, dpp_partner(v, 3));
+}
+// a wave-uniform 64-bit value into scalar registers
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+  int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
+  int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return ((int64_t)hi << 32) | (uint32_t)lo;
+}
+// q -> three balanced base-256 digits (each as a byte) of the 24-bit fixed point of null_i8.hip: the low byte of q, of
+// q1 = (q + 128) >> 8 and of (q1 + 128) >> 8.  (q1 is the (q - e0) >> 8 of the signed low digit e0 = ((q + 128) & 255) - 128:
+// the same three bytes for every |q| <= 8355711, checked over the whole range.)
+__device__ __forceinline__ void digits3(int q, unsigned& d0, unsigned& d1, unsigned& d2) {
+  const int q1 = (q + 128) >> 8;
+  d0 = (unsigned)q & 255u;
+  d1 = (unsigned)q1 & 255u;
+  d2 = (unsigned)((q1 + 128) >> 8) & 255u;
+}
 #endif

@@ -24,6 +24,9 @@
 #pragma clang fp contract(off)
 __device__ __forceinline__ double mul_rn(double a, double b) { return a * b; }
 __device__ __forceinline__ double add_rn(double a, double b) { return a + b; }
+// Below the pragma on purpose: the row pass of select_tail compiles uncontracted here (a multiply, then an add, where
+// rows.hip's copy of the same statements fuses them) -- the header sets no mode of its own.
+#include "rowstd.h"
 
 namespace {
 
@@ -95,185 +98,43 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
   return __hiloint2double(hi, lo);
 }
 
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-  int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
-  int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return ((int64_t)hi << 32) | (uint32_t)lo;
-}
-
 // write-out shared by both step kernels: s[] holds the new unscaled state of one row; element k
-// of lane `lane` is column col_of(lane, k)
-struct ColStride1 {   // one double per lane: col = lane + 64*k
-  __device__ static int col(int lane, int k) { return lane + 64 * k; }
-};
-struct ColPair {      // double2 per lane: cols 2*(lane + 64*(k/2)) + (k&1)
-  __device__ static int col(int lane, int k) { return 2 * (lane + 64 * (k >> 1)) + (k & 1); }
-};
-
-struct ColQuad {      // four adjacent columns per lane (4-byte state: one float4): cols 4*(lane + 64*(k/4)) + (k&3)
-  __device__ static int col(int lane, int k) { return 4 * (lane + 64 * (k >> 2)) + (k & 3); }
-};
+// of lane `lane` is column CM::col(lane, k) (rowstd.h: ColStride1, ColPair, ColQuad)
 
 // What rows.hip:k_select_std16 makes of a NAM row when every cell and every sample stays and nothing is regressed out
 // (_association.py:182 zero-variance count, _nam.py:122 centring, :159 division by the std with ddof = 1,
 // _association.py:77 coefficient X.y/N, the 24-bit digit planes of null_i8.hip), done by the wave that has just
-// formed the row: x[] holds s/C in the ColPair layout (lane l: columns 2l, 2l+1, 128+2l, ...).  Same statements as
-// that kernel; its sums run over 16 lanes x 4 columns, these over 64 lanes x 2, so the results agree to rounding.
-template <int NV>
+// formed the row: x[] holds s/C in the layout CM of the step kernel (ColPair, or ColQuad with the 4-byte state).  The
+// same row pass as that kernel (rowstd.h); its sums run over 16 lanes x 4 columns, these over 64 lanes, and this file
+// does not contract, so the results agree to rounding.
+template <int NV, typename CM>
 __device__ __forceinline__ void select_tail(const StepArgs& a, int64_t row, int lane, double (&x)[NV]) {
+  static_assert(!std::is_same<CM, ColStride1>::value, "X and the planes leave in pairs / quads of adjacent columns");
   const double n = (double)a.width;
   double sum = 0.0;
 #pragma unroll
   for (int k = 0; k < NV; ++k) sum += x[k];
-  const double avg0 = wave_sum(sum) / n;
-  bool flat = true;
-#pragma unroll
-  for (int k = 0; k < NV; ++k)
-    if (ColPair::col(lane, k) < a.width) flat = flat && (avg0 - x[k] == 0.0);
-  if (__all(flat) && lane == 0) atomicAdd(a.sel_nz, 1ull);
-#pragma unroll
-  for (int k = 0; k < NV; ++k)
-    if (ColPair::col(lane, k) < a.width) x[k] -= avg0;
-  double s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) s2 += x[k];
-  const double avg = wave_sum(s2) / n;
-  double ss = 0.0;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    if (ColPair::col(lane, k) < a.width) {
-      const double d = avg - x[k];
-      ss += d * d;
-    }
-  }
-  const double sd = sqrt(wave_sum(ss) / (n - 1.0));
-  double dot = 0.0, amax = 0.0;
+  const RowStd o = row_standardize<Wave64, CM>(x, sum, lane, a.width, true, a.sel_nz, NoProjector(),
+                                               [&](double& dot, int k, double xs) {
+    const int c = CM::col(lane, k);
+    if (c < a.width) dot += a.sel_y[c] * xs;
+  });
   double* __restrict__ dst = a.sel_X + row * a.sel_ldx;
 #pragma unroll
   for (int k = 0; k < NV; k += 2) {
-    const int c0 = ColPair::col(lane, k);
-    const double x0 = c0 < a.width ? __ddiv_rn(x[k], sd) : 0.0;
-    const double x1 = c0 + 1 < a.width ? __ddiv_rn(x[k + 1], sd) : 0.0;
-    x[k] = x0;
-    x[k + 1] = x1;
-    if (c0 < a.width) dot += a.sel_y[c0] * x0;
-    if (c0 + 1 < a.width) dot += a.sel_y[c0 + 1] * x1;
-    amax = fmax(amax, fmax(fabs(x0), fabs(x1)));          // NaN rows (zero variance): fmax drops them, q = 0 below
-    if (c0 + 1 < a.sel_ldx) *(double2*)(dst + c0) = make_double2(x0, x1);
+    const int c0 = CM::col(lane, k);
+    if (c0 + 1 < a.sel_ldx) *(double2*)(dst + c0) = make_double2(x[k], x[k + 1]);
   }
   if (a.sel_xq) {
-    const double rmax = wave_max_d(amax);
-    const double inv = rmax > 0.0 ? I8_QMAX / rmax : 0.0;
-    unsigned char* rq = a.sel_xq + (size_t)row * 3 * a.sel_Kp;
-#pragma unroll
-    for (int k = 0; k < NV; k += 2) {
-      unsigned h0 = 0, h1 = 0, h2 = 0;                      // this lane's two bytes of each plane
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const double v = x[k + j] * inv;
-        const int qi = v == v ? (int)rint(v) : 0;
-        const int q1 = (qi + 128) >> 8;
-        h0 |= ((unsigned)qi & 255u) << (8 * j);
-        h1 |= ((unsigned)q1 & 255u) << (8 * j);
-        h2 |= ((unsigned)((q1 + 128) >> 8) & 255u) << (8 * j);
-      }
-      // even lanes store dwords: their own half and the odd neighbour's
-      const unsigned p01 = h0 | (h1 << 16);
-      const unsigned o01 = (unsigned)__builtin_amdgcn_ds_bpermute(4 * (lane + 1), (int)p01);
-      const unsigned o2 = (unsigned)__builtin_amdgcn_ds_bpermute(4 * (lane + 1), (int)h2);
-      const int c0 = ColPair::col(lane, k);
-      if ((lane & 1) == 0 && c0 < a.sel_Kp) {
-        *(unsigned*)(rq + c0) = (p01 & 0xffffu) | (o01 << 16);
-        *(unsigned*)(rq + a.sel_Kp + c0) = (p01 >> 16) | (o01 & 0xffff0000u);
-        *(unsigned*)(rq + 2 * a.sel_Kp + c0) = (h2 & 0xffffu) | (o2 << 16);
-      }
-    }
-    const double l1 = rmax > 0.0 ? n * (I8_QMAX / rmax) + n : 0.0;
-    if (lane == 0) a.sel_xscale[row] = make_double2(rmax, l1);
+    const double rmax = wave_max_d(o.amax);
+    store_planes(CM(), x, i8_inv(rmax), lane, a.sel_xq + (size_t)row * 3 * a.sel_Kp, a.sel_Kp, true);
+    if (lane == 0) a.sel_xscale[row] = i8_row_scale(rmax, n);
   }
-  const double v = wave_sum(dot) / n;
+  const double v = wave_sum(o.dot) / n;
   if (lane == 0) {
     a.sel_nc[row] = v;
-    const unsigned long long bits = v != v ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(fabs(v));
+    const unsigned long long bits = coef_max_bits(fabs(v), v != v);
     // the maximum over all rows: most waves find the word already above their value and skip the atomic
-    if (bits > __builtin_nontemporal_load(a.sel_nz + 1)) atomicMax(a.sel_nz + 1, bits);
-  }
-}
-
-// The same statements for the four-columns-per-lane layout of k_nam_step32 (ColQuad).  A lane holds four adjacent bytes of
-// each digit plane, so the planes are stored as dwords without the exchange between neighbouring lanes.
-template <int NV>
-__device__ __forceinline__ void select_tail_quad(const StepArgs& a, int64_t row, int lane, double (&x)[NV]) {
-  const double n = (double)a.width;
-  double sum = 0.0;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) sum += x[k];
-  const double avg0 = wave_sum(sum) / n;
-  bool flat = true;
-#pragma unroll
-  for (int k = 0; k < NV; ++k)
-    if (ColQuad::col(lane, k) < a.width) flat = flat && (avg0 - x[k] == 0.0);
-  if (__all(flat) && lane == 0) atomicAdd(a.sel_nz, 1ull);
-#pragma unroll
-  for (int k = 0; k < NV; ++k)
-    if (ColQuad::col(lane, k) < a.width) x[k] -= avg0;
-  double s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) s2 += x[k];
-  const double avg = wave_sum(s2) / n;
-  double ss = 0.0;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    if (ColQuad::col(lane, k) < a.width) {
-      const double d = avg - x[k];
-      ss += d * d;
-    }
-  }
-  const double sd = sqrt(wave_sum(ss) / (n - 1.0));
-  double dot = 0.0, amax = 0.0;
-  double* __restrict__ dst = a.sel_X + row * a.sel_ldx;
-#pragma unroll
-  for (int k = 0; k < NV; k += 2) {
-    const int c0 = ColQuad::col(lane, k);
-    const double x0 = c0 < a.width ? __ddiv_rn(x[k], sd) : 0.0;
-    const double x1 = c0 + 1 < a.width ? __ddiv_rn(x[k + 1], sd) : 0.0;
-    x[k] = x0;
-    x[k + 1] = x1;
-    if (c0 < a.width) dot += a.sel_y[c0] * x0;
-    if (c0 + 1 < a.width) dot += a.sel_y[c0 + 1] * x1;
-    amax = fmax(amax, fmax(fabs(x0), fabs(x1)));
-    if (c0 + 1 < a.sel_ldx) *(double2*)(dst + c0) = make_double2(x0, x1);
-  }
-  if (a.sel_xq) {
-    const double rmax = wave_max_d(amax);
-    const double inv = rmax > 0.0 ? I8_QMAX / rmax : 0.0;
-    unsigned char* rq = a.sel_xq + (size_t)row * 3 * a.sel_Kp;
-#pragma unroll
-    for (int k = 0; k < NV; k += 4) {
-      unsigned h0 = 0, h1 = 0, h2 = 0;                      // this lane's four bytes of each plane
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const double v = x[k + j] * inv;
-        const int qi = v == v ? (int)rint(v) : 0;
-        const int q1 = (qi + 128) >> 8;
-        h0 |= ((unsigned)qi & 255u) << (8 * j);
-        h1 |= ((unsigned)q1 & 255u) << (8 * j);
-        h2 |= ((unsigned)((q1 + 128) >> 8) & 255u) << (8 * j);
-      }
-      const int c0 = ColQuad::col(lane, k);
-      if (c0 < a.sel_Kp) {
-        *(unsigned*)(rq + c0) = h0;
-        *(unsigned*)(rq + a.sel_Kp + c0) = h1;
-        *(unsigned*)(rq + 2 * a.sel_Kp + c0) = h2;
-      }
-    }
-    const double l1 = rmax > 0.0 ? n * (I8_QMAX / rmax) + n : 0.0;
-    if (lane == 0) a.sel_xscale[row] = make_double2(rmax, l1);
-  }
-  const double v = wave_sum(dot) / n;
-  if (lane == 0) {
-    a.sel_nc[row] = v;
-    const unsigned long long bits = v != v ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(fabs(v));
     if (bits > __builtin_nontemporal_load(a.sel_nz + 1)) atomicMax(a.sel_nz + 1, bits);
   }
 }
@@ -332,11 +193,8 @@ __device__ __forceinline__ void finish_row(const StepArgs& a, int64_t row, int64
       const double k4 = (m2 <= em * em) ? __builtin_nan("") : m4 / (m2 * m2);
       if (lane == 0) a.stat[grow] = k4 - 3.0;
     }
-    if constexpr (BYP && std::is_same<CM, ColPair>::value) {
-      if (a.sel_X) select_tail<NV>(a, row, lane, x);
-    }
-    if constexpr (BYP && std::is_same<CM, ColQuad>::value) {
-      if (a.sel_X) select_tail_quad<NV>(a, row, lane, x);
+    if constexpr (BYP) {
+      if (a.sel_X) select_tail<NV, CM>(a, row, lane, x);
     }
   }
 }

@@ -9,6 +9,7 @@
 //   A[i][k]: i = lane & 15, k = lane >> 4        B[k][j]: k = lane >> 4, j = lane & 15
 //   D[r][j]: r = (lane >> 4) + 4*reg, j = lane & 15,  reg in 0..3
 #include "common.h"
+#include "rowstd.h"
 #include <algorithm>
 #include <array>
 #include <cstdlib>
@@ -375,18 +376,6 @@ __global__ __launch_bounds__(64 * NW) void k_gram_blk(const double* __restrict__
 // neighbourhood coefficients (X.y/N, _association.py:77) and the zero-variance count on the way.  X is read by
 // nobody before the local null any more: 3.2 GB less traffic and one launch less at 2M x 200.  Same slabs per
 // workgroup, same order of the MFMAs and of k_gram_reduce: G is bit-identical to k_select_std16 + k_gram_blk.
-__device__ __forceinline__ double sg_row16_sum(double v) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  return dpp_add(v, 3);
-}
-__device__ __forceinline__ double sg_row16_max(double v) {
-  v = fmax(v, dpp_partner(v, 0));
-  v = fmax(v, dpp_partner(v, 1));
-  v = fmax(v, dpp_partner(v, 2));
-  return fmax(v, dpp_partner(v, 3));
-}
 __device__ __forceinline__ void sg_dma16(const void* gsrc, unsigned lds_base) {      // 16 bytes per lane, LDS = base + 16 lane
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -455,7 +444,8 @@ __global__ __launch_bounds__(512) void k_selgram_blk(const double* __restrict__ 
   // waves 0-7: rows 4 wv + r4 of the slab from `raw` into `buf` (and out to memory)
   // Registers are scarce here (nine accumulator tiles per lane stay live): every pass over the row re-reads its four
   // columns per group from LDS instead of keeping the row in registers -- the same values, the same operations in
-  // the same order as rows.hip:k_select_std16.
+  // the same order as rows.hip:k_select_std16.  So it takes rowstd.h's leaf helpers and not row_standardize: that one
+  // centres, projects and divides a register array in place, 4 G more live doubles where 256 registers already spill.
   auto standardize = [&](int64_t slab) {
     const int srow = 4 * wv + r4;
     const int64_t row = slab * SLAB + srow;
@@ -467,7 +457,7 @@ __global__ __launch_bounds__(512) void k_selgram_blk(const double* __restrict__ 
     for (int g = 0; g < G; ++g)
 #pragma unroll
       for (int j = 0; j < 4; ++j) sum += rawval(64 * g + 4 * l16 + j);
-    const double avg0 = sg_row16_sum(sum) / n;
+    const double avg0 = row16_sum(sum) / n;
     bool flat = true;
     double s2 = 0.0;
 #pragma unroll
@@ -482,12 +472,8 @@ __global__ __launch_bounds__(512) void k_selgram_blk(const double* __restrict__ 
         }
         s2 += xv;
       }
-    {
-      const unsigned long long bal = __ballot(flat);
-      const unsigned long long rowmask = 0xffffull << (16 * r4);
-      if (live && l16 == 0 && (bal & rowmask) == rowmask) atomicAdd(nzero, 1ull);
-    }
-    const double avg = sg_row16_sum(s2) / n;
+    if (Row16::all(flat, lane) && live && l16 == 0) atomicAdd(nzero, 1ull);
+    const double avg = row16_sum(s2) / n;
     double ss = 0.0;
 #pragma unroll
     for (int g = 0; g < G; ++g)
@@ -501,7 +487,7 @@ __global__ __launch_bounds__(512) void k_selgram_blk(const double* __restrict__ 
           ss += d * d;
         }
       }
-    const double sd = sqrt(sg_row16_sum(ss) / (n - 1.0));
+    const double sd = sqrt(row16_sum(ss) / (n - 1.0));
     double dot = 0.0, amax = 0.0;
     double* __restrict__ dst = X + row * ldx;
 #pragma unroll
@@ -534,41 +520,34 @@ __global__ __launch_bounds__(512) void k_selgram_blk(const double* __restrict__ 
       }
     }
     if (xq) {
-      const double rmax = sg_row16_max(amax);
-      const double inv = rmax > 0.0 ? I8_QMAX / rmax : 0.0;
+      const double rmax = row16_max(amax);
+      const double inv = i8_inv(rmax);
       unsigned* rq = (unsigned*)(xq + (size_t)row * 3 * Kp);
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         const int c0 = 64 * g + 4 * l16;
-        unsigned w0 = 0, w1 = 0, w2 = 0;
+        double xs4[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           double xv = rawval(c0 + j);                  // the standardised value again (the slab may be narrower than Kp)
           if (c0 + j < Nx) xv -= avg0;
-          const double xs = c0 + j < Nx ? __ddiv_rn(xv, sd) : 0.0;
-          const double v = xs * inv;
-          const int qi = v == v ? (int)rint(v) : 0;
-          const int q1 = (qi + 128) >> 8;
-          w0 |= ((unsigned)qi & 255u) << (8 * j);
-          w1 |= ((unsigned)q1 & 255u) << (8 * j);
-          w2 |= ((unsigned)((q1 + 128) >> 8) & 255u) << (8 * j);
+          xs4[j] = c0 + j < Nx ? __ddiv_rn(xv, sd) : 0.0;
         }
+        unsigned w0, w1, w2;
+        i8_pack<4>(xs4, inv, w0, w1, w2);
         if (live && c0 < Kp) {
           rq[c0 >> 2] = w0;
           rq[(Kp + c0) >> 2] = w1;
           rq[(2 * Kp + c0) >> 2] = w2;
         }
       }
-      const double l1 = rmax > 0.0 ? n * (I8_QMAX / rmax) + n : 0.0;
-      if (live && l16 == 0) xscale[row] = make_double2(rmax, l1);
+      if (live && l16 == 0) xscale[row] = i8_row_scale(rmax, n);
     }
     if (y) {
-      const double v = sg_row16_sum(dot) / n;
+      const double v = row16_sum(dot) / n;
       if (live) {
         if (l16 == 0) nc[row] = v;
-        const double av = fabs(v);
-        if (av > vmax) vmax = av;
-        any_nan = any_nan || (v != v);
+        coef_note(v, vmax, any_nan);
       }
     }
   };
@@ -632,19 +611,7 @@ __global__ __launch_bounds__(512) void k_selgram_blk(const double* __restrict__ 
         for (int r = 0; r < 4; ++r) p[r * 64 + lane] = acc[h][t][r];
       }
     }
-  if (y) {
-    {
-      const bool wn = __any(any_nan);
-      const double wm = wave_max_d(vmax);
-      if (lane == 0) wmax[wv] = wn ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(wm);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long m = wmax[0];
-      for (int i = 1; i < 8; ++i) m = wmax[i] > m ? wmax[i] : m;
-      blockmax[blockIdx.x] = m;
-    }
-  }
+  if (y) coef_max_epilogue<NW, true>(wmax, lane, wv, vmax, any_nan, blockmax);
 }
 
 // The same with two LDS slabs: the next slab's global loads are issued before the MFMAs of the current one

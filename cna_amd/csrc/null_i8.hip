@@ -39,17 +39,6 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 #define I8_DROP (2.0 * 128 * 128 * 256 + 128.0 * 128 + 0.25)
 #define I8_QBUF 192
 
-// q -> three balanced base-256 digits (each as a byte)
-__device__ __forceinline__ void digits3(int q, unsigned& d0, unsigned& d1, unsigned& d2) {
-  const int e0 = ((q + 128) & 255) - 128;
-  const int q1 = (q - e0) >> 8;
-  const int e1 = ((q1 + 128) & 255) - 128;
-  const int e2 = (q1 - e1) >> 8;
-  d0 = (unsigned)e0 & 255u;
-  d1 = (unsigned)e1 & 255u;
-  d2 = (unsigned)e2 & 255u;
-}
-
 // max |Yc| over the N x P block (positive doubles order like their bit patterns)
 __global__ __launch_bounds__(1024) void k_y_absmax(const double* __restrict__ Y, int ldy, int N, int P,
                                                    unsigned long long* __restrict__ scal) {

@@ -3,15 +3,10 @@
 // All matrices are cell-major (one row per cell), so every statistic "over samples" is a
 // reduction inside one row: one wave per row, lanes across the sample axis.
 #include "common.h"
+#include "rowstd.h"
 #include <cstddef>
 
 namespace {
-
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-  int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
-  int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return ((int64_t)hi << 32) | (uint32_t)lo;
-}
 
 constexpr int MAXQ = 16;  // up to 1024 columns per row
 
@@ -264,17 +259,7 @@ __global__ __launch_bounds__(256) void k_standardize(double* __restrict__ X, int
           sum[r] += x[r][q];
         }
       }
-      // pandas std: avg = sum/N ; sqrt(sum((avg-x)^2)/(N-1))
-      const double avg = wave_sum(sum[r]) / n;
-      double ss = 0.0;
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        if (lane + 64 * q < Nx) {
-          const double d = avg - x[r][q];
-          ss += d * d;
-        }
-      }
-      const double sd = sqrt(wave_sum(ss) / (n - 1.0));
+      const double sd = row_sd<Wave64, ColStride1>(x[r], sum[r], lane, Nx);
       if (base + r < nx) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -328,6 +313,25 @@ __global__ __launch_bounds__(256) void k_select_std(const double* __restrict__ n
     sc[q] = col < Nx ? (colmap ? colmap[col] : col) : 0;
     yv[q] = (y && col < Nx) ? y[col] : 0.0;
   }
+  auto project = [&](double (&xr)[NQ]) {                     // x <- x - (x.W^T).C^T
+    if (rk > 0) {
+      double corr[NQ];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) corr[q] = 0.0;
+      for (int k = 0; k < rk; ++k) {
+        double d = 0.0;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+          if (lane + 64 * q < Nx) d += xr[q] * Wl[k * Nx + lane + 64 * q];
+        const double pk = wave_sum(d);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+          if (lane + 64 * q < Nx) corr[q] += pk * Ctl[k * Nx + lane + 64 * q];
+      }
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) xr[q] -= corr[q];
+    }
+  };
   double vmax = 0.0;
   bool any_nan = false;
   for (int64_t base = ((int64_t)blockIdx.x * 4 + wv) * RPW; base < nx; base += stride) {
@@ -347,60 +351,16 @@ __global__ __launch_bounds__(256) void k_select_std(const double* __restrict__ n
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
       if (base + r >= nx) break;                         // wave-uniform
-      // zero variance the way pandas sees it: avg = sum/N, every (avg - x) == 0
-      const double avg0 = wave_sum(sum[r]) / n;
-      bool flat = true;
-#pragma unroll
-      for (int q = 0; q < NQ; ++q)
-        if (lane + 64 * q < Nx) flat = flat && (avg0 - x[r][q] == 0.0);
-      if (__all(flat) && lane == 0) atomicAdd(nzero, 1ull);
-      // centre (_nam.py:122), then std with ddof=1 of the centred values (_nam.py:159)
-      double s2 = 0.0;
-#pragma unroll
-      for (int q = 0; q < NQ; ++q)
-        if (lane + 64 * q < Nx) x[r][q] -= avg0;
-      if (rk > 0) {                                          // x <- x - (x.W^T).C^T
-        double corr[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) corr[q] = 0.0;
-        for (int k = 0; k < rk; ++k) {
-          double d = 0.0;
-#pragma unroll
-          for (int q = 0; q < NQ; ++q)
-            if (lane + 64 * q < Nx) d += x[r][q] * Wl[k * Nx + lane + 64 * q];
-          const double pk = wave_sum(d);
-#pragma unroll
-          for (int q = 0; q < NQ; ++q)
-            if (lane + 64 * q < Nx) corr[q] += pk * Ctl[k * Nx + lane + 64 * q];
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) x[r][q] -= corr[q];
-      }
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) s2 += x[r][q];
-      const double avg = wave_sum(s2) / n;
-      double ss = 0.0;
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        if (lane + 64 * q < Nx) {
-          const double d = avg - x[r][q];
-          ss += d * d;
-        }
-      }
-      const double sd = sqrt(wave_sum(ss) / (n - 1.0));
-      double dot = 0.0, amax = 0.0;
+      const RowStd o = row_standardize<Wave64, ColStride1>(x[r], sum[r], lane, Nx, true, nzero, project,
+                                                          [&](double& dot, int q, double xs) { dot += yv[q] * xs; });
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         const int col = lane + 64 * q;
-        const double xs = col < Nx ? __ddiv_rn(x[r][q], sd) : 0.0;
-        if (col < ldx) X[(base + r) * ldx + col] = xs;
-        dot += yv[q] * xs;
-        x[r][q] = xs;
-        amax = fmax(amax, fabs(xs));                      // NaN rows (zero variance): fmax drops them, q = 0 below
+        if (col < ldx) X[(base + r) * ldx + col] = x[r][q];
       }
       if (xq) {
-        const double rmax = wave_max_d(amax);
-        const double inv = rmax > 0.0 ? I8_QMAX / rmax : 0.0;
+        const double rmax = wave_max_d(o.amax);
+        const double inv = i8_inv(rmax);
         // bytes of a row meet in LDS (one plane = 256 bytes per wave) and leave as dwords: three 4 Kp / 4-lane stores
         // per row instead of twelve byte stores (partial-line writes: +0.6 ms at 2M x 200)
         unsigned char* qb = (unsigned char*)qstage[wv];
@@ -408,13 +368,11 @@ __global__ __launch_bounds__(256) void k_select_std(const double* __restrict__ n
         for (int q = 0; q < NQ; ++q) {
           const int col = lane + 64 * q;
           if (col < Kp) {
-            const double v = x[r][q] * inv;
-            const int qi = v == v ? (int)rint(v) : 0;
-            // balanced base-256 digits: the low byte of qi, of (qi + 128) >> 8 and of ((qi + 128) >> 8) + 128 >> 8
-            const int q1 = (qi + 128) >> 8;
-            qb[col] = (unsigned char)qi;
-            qb[256 + col] = (unsigned char)q1;
-            qb[512 + col] = (unsigned char)((q1 + 128) >> 8);
+            unsigned d0, d1, d2;
+            i8_bytes(x[r][q], inv, d0, d1, d2);
+            qb[col] = (unsigned char)d0;
+            qb[256 + col] = (unsigned char)d1;
+            qb[512 + col] = (unsigned char)d2;
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -425,52 +383,25 @@ __global__ __launch_bounds__(256) void k_select_std(const double* __restrict__ n
           rq[2 * (Kp / 4) + lane] = qstage[wv][128 + lane];
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // sum |q| from above instead of a reduction: the row has sum x^2 = N - 1, so sum |x| < N and
-        // sum |q| <= N Q / max|x| + N / 2
-        const double l1 = rmax > 0.0 ? n * (I8_QMAX / rmax) + n : 0.0;
-        if (lane == 0) xscale[base + r] = make_double2(rmax, l1);
+        if (lane == 0) xscale[base + r] = i8_row_scale(rmax, n);
       }
       if (y) {
-        const double v = wave_sum(dot) / n;
+        const double v = wave_sum(o.dot) / n;
         if (lane == 0) nc[base + r] = v;
-        const double av = fabs(v);
-        if (av > vmax) vmax = av;
-        any_nan = any_nan || (v != v);
+        coef_note(v, vmax, any_nan);
       }
     }
   }
-  if (y) {                                   // one slot per workgroup, folded by k_max_fold (see k_ncorrs)
-    if (lane == 0)
-      wmax[wv] = any_nan ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(vmax);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long m = wmax[0];
-      for (int i = 1; i < 4; ++i) m = wmax[i] > m ? wmax[i] : m;
-      blockmax[blockIdx.x] = m;
-    }
-  }
+  if (y) coef_max_epilogue<4, false>(wmax, lane, wv, vmax, any_nan, blockmax);
 }
 
-// The same pass for up to 256 samples with SIXTEEN lanes per cell, four cells per wave: lane (r = lane >> 4,
-// l = lane & 15) owns the columns 64 g + 4 l + j (g < G, j < 4) of row base + r.  The row statistics (mean,
-// mean of the centred values, sum of squares, coefficient, max |x|) are then four DPP steps inside a row of 16
-// lanes -- no cross-row combination through scalar reads, which made the wave-per-row kernel VALU-bound
+// The same pass for up to 256 samples with SIXTEEN lanes per cell, four cells per wave, and no projector: lane
+// (r = lane >> 4, l = lane & 15) owns the columns 64 g + 4 l + j (g < G, j < 4) of row base + r (ColQuad16).  The row
+// statistics (mean, mean of the centred values, sum of squares, coefficient, max |x|) are then four DPP steps inside
+// a row of 16 lanes -- no cross-row combination through scalar reads, which made the wave-per-row kernel VALU-bound
 // (400 instructions per cell, 8.0e8 per launch at 2M x 200: 1.5 ms of issue for a 1.2 ms stream) -- and four
 // consecutive columns per lane are one 32-byte load, one 32-byte store and, for the digit planes, one dword
 // per plane without a detour through LDS.
-__device__ __forceinline__ double row16_sum(double v) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  return dpp_add(v, 3);
-}
-__device__ __forceinline__ double row16_max(double v) {
-  v = fmax(v, dpp_partner(v, 0));
-  v = fmax(v, dpp_partner(v, 1));
-  v = fmax(v, dpp_partner(v, 2));
-  return fmax(v, dpp_partner(v, 3));
-}
-
 template <int G>
 __global__ __launch_bounds__(256) void k_select_std16(const double* __restrict__ nam, int ld,
                                                       const int64_t* __restrict__ keep,
@@ -478,14 +409,8 @@ __global__ __launch_bounds__(256) void k_select_std16(const double* __restrict__
                                                       int64_t nx, int Nx, int ldx, unsigned long long* nzero,
                                                       const double* __restrict__ y, double* __restrict__ nc,
                                                       unsigned long long* __restrict__ blockmax,
-                                                      const double* __restrict__ Wg, const double* __restrict__ Ctg, int rk,
                                                       unsigned char* __restrict__ xq, double2* __restrict__ xscale, int Kp) {
-  extern __shared__ double lw[];
   __shared__ unsigned long long wmax[4];
-  for (int i = threadIdx.x; i < 2 * rk * Nx; i += 256) lw[i] = i < rk * Nx ? Wg[i] : Ctg[i - rk * Nx];
-  if (rk > 0) __syncthreads();
-  const double* Wl = lw;
-  const double* Ctl = lw + (size_t)rk * Nx;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r4 = lane >> 4, l16 = lane & 15;
@@ -528,68 +453,12 @@ __global__ __launch_bounds__(256) void k_select_std16(const double* __restrict__
 #pragma unroll
       for (int j = 0; j < 4; ++j) sum += x[4 * g + j];
     }
-    // zero variance the way pandas sees it: avg = sum/N, every (avg - x) == 0
-    const double avg0 = row16_sum(sum) / n;
-    bool flat = true;
+    const RowStd o = row_standardize<Row16, ColQuad16>(x, sum, lane, Nx, live, nzero, NoProjector(),
+                                                       [&](double& dot, int e, double xs) { dot += yv[e] * xs; });
+    if (live) {
+      double* __restrict__ dst = X + row * ldx;
 #pragma unroll
-    for (int e = 0; e < NE; ++e)
-      if (64 * (e >> 2) + 4 * l16 + (e & 3) < Nx) flat = flat && (avg0 - x[e] == 0.0);
-    {
-      const unsigned long long bal = __ballot(flat);
-      const unsigned long long rowmask = 0xffffull << (16 * r4);
-      if (live && l16 == 0 && (bal & rowmask) == rowmask) atomicAdd(nzero, 1ull);
-    }
-    // centre (_nam.py:122), then std with ddof=1 of the centred values (_nam.py:159)
-#pragma unroll
-    for (int e = 0; e < NE; ++e)
-      if (64 * (e >> 2) + 4 * l16 + (e & 3) < Nx) x[e] -= avg0;
-    if (rk > 0) {                                            // x <- x - (x.W^T).C^T
-      double corr[NE];
-#pragma unroll
-      for (int e = 0; e < NE; ++e) corr[e] = 0.0;
-      for (int k = 0; k < rk; ++k) {
-        double d = 0.0;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-          const int col = 64 * (e >> 2) + 4 * l16 + (e & 3);
-          if (col < Nx) d += x[e] * Wl[k * Nx + col];
-        }
-        const double pk = row16_sum(d);
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-          const int col = 64 * (e >> 2) + 4 * l16 + (e & 3);
-          if (col < Nx) corr[e] += pk * Ctl[k * Nx + col];
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < NE; ++e) x[e] -= corr[e];
-    }
-    double s2 = 0.0;
-#pragma unroll
-    for (int e = 0; e < NE; ++e) s2 += x[e];
-    const double avg = row16_sum(s2) / n;
-    double ss = 0.0;
-#pragma unroll
-    for (int e = 0; e < NE; ++e) {
-      if (64 * (e >> 2) + 4 * l16 + (e & 3) < Nx) {
-        const double d = avg - x[e];
-        ss += d * d;
-      }
-    }
-    const double sd = sqrt(row16_sum(ss) / (n - 1.0));
-    double dot = 0.0, amax = 0.0;
-    double* __restrict__ dst = X + row * ldx;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = 4 * g + j, col = 64 * g + 4 * l16 + j;
-        const double xs = col < Nx ? __ddiv_rn(x[e], sd) : 0.0;
-        x[e] = xs;
-        dot += yv[e] * xs;
-        amax = fmax(amax, fabs(xs));                      // NaN rows (zero variance): fmax drops them, q = 0 below
-      }
-      if (live) {
+      for (int g = 0; g < G; ++g) {
         const int c0 = 64 * g + 4 * l16;
         if (c0 + 3 < ldx && (ldx & 1) == 0) {
           *(double2*)(dst + c0) = make_double2(x[4 * g], x[4 * g + 1]);
@@ -602,55 +471,19 @@ __global__ __launch_bounds__(256) void k_select_std16(const double* __restrict__
       }
     }
     if (xq) {
-      const double rmax = row16_max(amax);
-      const double inv = rmax > 0.0 ? I8_QMAX / rmax : 0.0;
-      unsigned* rq = (unsigned*)(xq + (size_t)row * 3 * Kp);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        unsigned w0 = 0, w1 = 0, w2 = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const double v = x[4 * g + j] * inv;
-          const int qi = v == v ? (int)rint(v) : 0;
-          // balanced base-256 digits: the low byte of qi, of (qi + 128) >> 8 and of ((qi + 128) >> 8) + 128 >> 8
-          const int q1 = (qi + 128) >> 8;
-          w0 |= ((unsigned)qi & 255u) << (8 * j);
-          w1 |= ((unsigned)q1 & 255u) << (8 * j);
-          w2 |= ((unsigned)((q1 + 128) >> 8) & 255u) << (8 * j);
-        }
-        const int c0 = 64 * g + 4 * l16;
-        if (live && c0 < Kp) {
-          rq[c0 >> 2] = w0;
-          rq[(Kp + c0) >> 2] = w1;
-          rq[(2 * Kp + c0) >> 2] = w2;
-        }
-      }
-      // sum |q| from above instead of a reduction: the row has sum x^2 = N - 1, so sum |x| < N and
-      // sum |q| <= N Q / max|x| + N / 2
-      const double l1 = rmax > 0.0 ? n * (I8_QMAX / rmax) + n : 0.0;
-      if (live && l16 == 0) xscale[row] = make_double2(rmax, l1);
+      const double rmax = row16_max(o.amax);
+      store_planes(ColQuad16(), x, i8_inv(rmax), lane, xq + (size_t)row * 3 * Kp, Kp, live);
+      if (live && l16 == 0) xscale[row] = i8_row_scale(rmax, n);
     }
     if (y) {
-      const double v = row16_sum(dot) / n;
+      const double v = row16_sum(o.dot) / n;
       if (live) {
         if (l16 == 0) nc[row] = v;
-        const double av = fabs(v);
-        if (av > vmax) vmax = av;
-        any_nan = any_nan || (v != v);
+        coef_note(v, vmax, any_nan);
       }
     }
   }
-  if (y) {                                   // one slot per workgroup, folded by k_max_fold (see k_ncorrs)
-    const bool wn = __any(any_nan);
-    const double wm = wave_max_d(vmax);
-    if (lane == 0) wmax[wv] = wn ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(wm);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long m = wmax[0];
-      for (int i = 1; i < 4; ++i) m = wmax[i] > m ? wmax[i] : m;
-      blockmax[blockIdx.x] = m;
-    }
-  }
+  if (y) coef_max_epilogue<4, true>(wmax, lane, wv, vmax, any_nan, blockmax);
 }
 
 // ---- X <- (X - mean).M^T for a projector of low rank defect, M = I - C.W (C: N x r standardised batches /
@@ -784,18 +617,7 @@ __global__ __launch_bounds__(256) void k_resid_lowrank(double* __restrict__ X, i
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
     double sd = 1.0;
-    if (standardize) {                          // pandas std: avg = sum/N ; sqrt(sum((avg-x)^2)/(N-1))
-      const double avg = wave_sum(s2) / n;
-      double ss = 0.0;
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        if (lane + 64 * q < Nx) {
-          const double dd = avg - x[q];
-          ss += dd * dd;
-        }
-      }
-      sd = sqrt(wave_sum(ss) / (n - 1.0));
-    }
+    if (standardize) sd = row_sd<Wave64, ColStride1>(x, s2, lane, Nx);
     double dot = 0.0;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -807,22 +629,11 @@ __global__ __launch_bounds__(256) void k_resid_lowrank(double* __restrict__ X, i
     if (y) {
       const double v = wave_sum(dot) / n;
       if (lane == 0) nc[row] = v;
-      const double av = fabs(v);
-      if (av > vmax) vmax = av;
-      any_nan = any_nan || (v != v);
+      coef_note(v, vmax, any_nan);
     }
    }
   }
-  if (y) {
-    if (lane == 0)
-      wmax[wv] = any_nan ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(vmax);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long m = wmax[0];
-      for (int i = 1; i < 4; ++i) m = wmax[i] > m ? wmax[i] : m;
-      blockmax[blockIdx.x] = m;
-    }
-  }
+  if (y) coef_max_epilogue<4, false>(wmax, lane, wv, vmax, any_nan, blockmax);
 }
 
 // ---- ncorrs = (y[:,None]*NAMresid).mean(axis=0) (_association.py:77) -----------------------
@@ -856,22 +667,11 @@ __global__ __launch_bounds__(256) void k_ncorrs(const double* __restrict__ X, in
       const double v = wave_sum(s[r]) / (double)Nx;
       if (base + r < nx) {
         if (lane == 0) out[base + r] = v;
-        const double av = fabs(v);
-        if (av > vmax) vmax = av;
-        any_nan = any_nan || (v != v);
+        coef_note(v, vmax, any_nan);
       }
     }
   }
-  // non-negative doubles order like their bit patterns; NaN (0x7ff8...) sorts above +inf.
-  // One slot per workgroup, folded by k_max_fold: 8192 same-address atomics cost ~80 us.
-  if (lane == 0)
-    wmax[wv] = any_nan ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(vmax);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long m = wmax[0];
-    for (int i = 1; i < 4; ++i) m = wmax[i] > m ? wmax[i] : m;
-    blockmax[blockIdx.x] = m;
-  }
+  coef_max_epilogue<4, false>(wmax, lane, wv, vmax, any_nan, blockmax);
 }
 
 // One pass of an exact radix select over doubles: histogram of the 8-bit digit at `shift` among the
@@ -1322,20 +1122,20 @@ int launch_select_std(cna_ctx* c, const int32_t* colmap_dev, unsigned long long*
   // (rows16.hip's sixteen-rows-per-wave pass with the projector on the matrix cores, extended by this pass's extras --
   // row selection, zero-variance count, digit planes -- measured slower here: 1217 against 785 us at 1M x 100 with three
   // covariates, 731 against 405 at 500k x 128; it serves the in-place ridge pass and the batch kurtosis only)
-  // sixteen lanes per cell up to 256 samples; with a projector the wave-per-cell kernel keeps the lead (its four
-  // cells share every LDS read of the factors: 2.42 vs 2.71 ms at 2M x 200 with 5 covariates)
+  // sixteen lanes per cell up to 256 samples.  With a projector the wave-per-cell kernel is the one that runs (its four
+  // cells share every LDS read of the factors: 2.42 ms against 2.71 ms for a 16-lane variant at 2M x 200 with 5
+  // covariates), so the 16-lane kernel carries none.  Nx <= 256 gives ldx <= 256 and Kp <= 256, hence G <= 4.
   if (c->Nx <= 256 && rk == 0) {
     const int cols = c->ldx > Kp ? c->ldx : Kp;
     const int G = (cols + 63) / 64;
+    if (G > 4) CNA_FAIL(CNA_EINVAL, "launch_select_std: more than 256 columns in the 16-lane selection kernel");
     const unsigned grid16 = wave_grid((c->nx + 3) / 4);      // 16 rows per workgroup and turn
-#define SS16(GG) { static bool once = false; if (smem > 48 * 1024 && !once) { HIP_TRY(hipFuncSetAttribute((const void*)k_select_std16<GG>, hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024)); once = true; } \
-    hipLaunchKernelGGL(k_select_std16<GG>, dim3(grid16), dim3(256), smem, c->stream, c->nam, c->ld, c->keep_idx, colmap_dev, c->X, c->nx, c->Nx, c->ldx, nzero_dev, y_dev, c->ncorrs, maxbits_dev ? maxbits_dev + 1 : nullptr, W_dev, Ct_dev, rk, xq, (double2*)xscale, Kp); }
+#define SS16(GG) hipLaunchKernelGGL(k_select_std16<GG>, dim3(grid16), dim3(256), 0, c->stream, c->nam, c->ld, c->keep_idx, colmap_dev, c->X, c->nx, c->Nx, c->ldx, nzero_dev, y_dev, c->ncorrs, maxbits_dev ? maxbits_dev + 1 : nullptr, xq, (double2*)xscale, Kp)
     switch (G) {
-      case 1: SS16(1) break;
-      case 2: SS16(2) break;
-      case 3: SS16(3) break;
-      case 4: SS16(4) break;
-      default: SS16(5) break;
+      case 1: SS16(1); break;
+      case 2: SS16(2); break;
+      case 3: SS16(3); break;
+      case 4: SS16(4); break;
     }
 #undef SS16
     if (y_dev) hipLaunchKernelGGL(k_max_fold, dim3(1), dim3(256), 0, c->stream, maxbits_dev + 1, (int)grid16, maxbits_dev);

@@ -18,18 +18,12 @@
 // relative).  The projections are taken from the uncentred row and corrected, p_k = x.w_k - mean (1.w_k): the columns
 // of C are centred, so 1.w_k is rounding noise and the two forms are the same number to a few ulps of |x|.
 #include "common.h"
+#include "rowstd.h"
 #include <cstdlib>
 
 namespace {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double r16_sum(double v) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  return dpp_add(v, 3);
-}
 
 // operands of k_rowpass16 in one device block: B1 [NP][16] (W^T, zero padded) | Ct [16][NP] | sw[16] = row sums of W |
 // inv_cnt[16] = 1 / samples of batch b | bcode[NP] (int32: batch of a column, -1 none)
@@ -74,13 +68,6 @@ __global__ __launch_bounds__(256) void k_rowpass16_prep(const double* __restrict
   }
 }
 
-__device__ __forceinline__ double r16_max(double v) {
-  v = fmax(v, dpp_partner(v, 0));
-  v = fmax(v, dpp_partner(v, 1));
-  v = fmax(v, dpp_partner(v, 2));
-  return fmax(v, dpp_partner(v, 3));
-}
-
 // batch kurtosis of row i of the register tile as it stands (_nam.py:78-82: Fisher kurtosis of the batch means, + 3)
 template <int NT>
 __device__ __forceinline__ double row_batch_kurtosis(const double (&xd)[NT][4], int i, const int (&code)[NT], int nb,
@@ -94,7 +81,7 @@ __device__ __forceinline__ double row_batch_kurtosis(const double (&xd)[NT][4], 
       double part = 0.0;
 #pragma unroll
       for (int t = 0; t < NT; ++t) part += code[t] == b ? xd[t][i] : 0.0;
-      bm[b] = r16_sum(part) * pinv[b];
+      bm[b] = row16_sum(part) * pinv[b];
       bsum += bm[b];
     }
   }
@@ -176,8 +163,8 @@ __global__ __launch_bounds__(256) void k_rowpass16(const double* __restrict__ sr
 #pragma unroll
         for (int t = 0; t < NT; ++t)
           if (16 * t + n < N) { hi = fmax(hi, xd[t][i]); lo = fmin(lo, xd[t][i]); }
-        hi = r16_max(hi);
-        lo = -r16_max(-lo);
+        hi = row16_max(hi);
+        lo = -row16_max(-lo);
         bool flat = hi == lo;
         if (flat) {                                          // pandas nanvar: zero iff sum / N == x (the sum taken in order)
           double s = 0.0;
@@ -194,7 +181,7 @@ __global__ __launch_bounds__(256) void k_rowpass16(const double* __restrict__ sr
         double s = 0.0;
 #pragma unroll
         for (int t = 0; t < NT; ++t) s += xd[t][i];
-        mean[i] = r16_sum(s) / nn;
+        mean[i] = row16_sum(s) / nn;
 #pragma unroll
         for (int t = 0; t < NT; ++t)
           if (16 * t + n < N) xd[t][i] -= mean[i];
@@ -220,9 +207,9 @@ __global__ __launch_bounds__(256) void k_rowpass16(const double* __restrict__ sr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int64_t row = row0 + g + 4 * i;
-          const double bmean = r16_sum(mine ? P[i] : 0.0) / nbd;
+          const double bmean = row16_sum(mine ? P[i] : 0.0) / nbd;
           const double d = mine ? P[i] - bmean : 0.0;
-          const double m2 = r16_sum(d * d) / nbd;
+          const double m2 = row16_sum(d * d) / nbd;
           const double em = 2.220446049250313e-16 * bmean;
           const bool nan_k = m2 <= em * em;
           if (n == 0 && row < nrows) {
@@ -265,7 +252,7 @@ __global__ __launch_bounds__(256) void k_rowpass16(const double* __restrict__ sr
         double s2 = 0.0;
 #pragma unroll
         for (int t = 0; t < NT; ++t) s2 += xd[t][i];
-        const double avg = r16_sum(s2) / nn;
+        const double avg = row16_sum(s2) / nn;
         double ss = 0.0;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -274,7 +261,7 @@ __global__ __launch_bounds__(256) void k_rowpass16(const double* __restrict__ sr
             ss += dd * dd;
           }
         }
-        sd = sqrt(r16_sum(ss) / (nn - 1.0));
+        sd = sqrt(row16_sum(ss) / (nn - 1.0));
       }
       double dot = 0.0;
 #pragma unroll
@@ -285,12 +272,10 @@ __global__ __launch_bounds__(256) void k_rowpass16(const double* __restrict__ sr
         dot += yv[t] * xs;
       }
       if (y) {
-        const double v = r16_sum(dot) / nn;
+        const double v = row16_sum(dot) / nn;
         if (row < nrows) {
           if (n == 0) nc[row] = v;
-          const double av = fabs(v);
-          if (av > vmax) vmax = av;
-          any_nan = any_nan || (v != v);
+          coef_note(v, vmax, any_nan);
         }
       }
     }
@@ -299,7 +284,7 @@ __global__ __launch_bounds__(256) void k_rowpass16(const double* __restrict__ sr
     const bool wn = __any(any_nan);
     const double wm = wave_max_d(vmax);
     if (lane == 0) {
-      const unsigned long long bits = wn ? 0x7ff8000000000000ull : (unsigned long long)__double_as_longlong(wm);
+      const unsigned long long bits = coef_max_bits(wm, wn);
       if (bits > __builtin_nontemporal_load(maxword)) atomicMax(maxword, bits);
     }
   }
