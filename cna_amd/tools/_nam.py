@@ -737,10 +737,28 @@ def _ridge_factors(C, n_batch_cols, ridge, N):
     return W, M
 
 
-def _lowrank_ok(engine, plan):
-    """Apply M = I - C.W in factored form (engine.resid_lowrank)?  When the engine has it and both factors
-    fit the kernel's LDS budget (2 r N doubles <= 128 KB)."""
-    return hasattr(engine, 'resid_lowrank') and 0 < plan.r and 2 * plan.r * plan.N * 8 <= 128 * 1024
+LOWRANK_LDS_BYTES = 128 * 1024
+
+
+def _x_ld(N):
+    """csrc/c_api.hip:x_ld -- the row stride of the working matrix X with N samples."""
+    ld = (N + 3) // 4 * 4
+    if ld > 128 and (ld * 8) % 256 == 0 and ld + 4 <= 256:
+        ld += 4
+    return ld
+
+
+def _lowrank_lds(r, N, bk=False):
+    """Dynamic LDS of csrc/rows.hip:launch_resid_lowrank, in bytes: W and C^T (2 r N doubles) and, when the batch
+    kurtosis rides along (cna_resid_lowrank_bk), one row of X per wave (4 x_ld(N) doubles)."""
+    return 8 * (2 * r * N + (4 * _x_ld(N) if bk else 0))
+
+
+def _lowrank_ok(engine, plan, bk=False):
+    """Apply M = I - C.W in factored form (engine.resid_lowrank; bk: engine.resid_lowrank_bk, the pass that carries the
+    batch kurtosis)?  When the engine has it and the kernel's LDS need (_lowrank_lds) is within what the library takes
+    -- 128 KB, where it refuses after X has been voided."""
+    return hasattr(engine, 'resid_lowrank') and 0 < plan.r and _lowrank_lds(plan.r, plan.N, bk) <= LOWRANK_LDS_BYTES
 
 
 def _resid_run(engine, plan, cell_index, show_progress=False):
@@ -779,7 +797,7 @@ def _resid_run(engine, plan, cell_index, show_progress=False):
             print('\twith ridge', plan.ridges[0], 'median batch kurtosis = ', plan.onepass[3], file=out)
             first = False
             done = True
-        elif (len(plan.ridges) and y_std is not None and _lowrank_ok(engine, plan) and hasattr(engine, 'resid_lowrank_bk')
+        elif (len(plan.ridges) and y_std is not None and _lowrank_ok(engine, plan, bk=True) and hasattr(engine, 'resid_lowrank_bk')
                 and getattr(plan, 'reselect', None) is not None and os.environ.get('CNA_RIDGE_ONEPASS', '1') not in ('0', 'off', 'no')):
             # The first ridge in ONE pass, optimistically: residualise, batch kurtosis (median taken on the device),
             # and -- assuming the schedule ends here, as it always does with up to seven batches -- the division by the
