@@ -48,6 +48,7 @@ SIGNATURES = {
     'cna_nam_auto_finish': (C.c_int, [c_ctx, C.POINTER(C.c_int), C.c_void_p]),
     'cna_stat_qc': (C.c_int, [c_ctx, c_f64p, c_f64p, c_i64p]),
     'cna_fetch_cell_stat': (C.c_int, [c_ctx, C.c_void_p, C.c_int64]),
+    'cna_load_cell_stat': (C.c_int, [c_ctx, C.c_void_p, C.c_int64]),
     'cna_dense_load': (C.c_int, [c_ctx, C.c_void_p, C.c_int]),
     'cna_dense_step': (C.c_int, [c_ctx]),
     'cna_dense_fetch': (C.c_int, [c_ctx, C.c_void_p]),

@@ -1100,6 +1100,23 @@ int cna_fetch_cell_stat(cna_ctx* c, double* out, int64_t n_expected) {
   return ragged_gather(c, c->stat, c->nx, out, n_expected);
 }
 
+// For tests: the caller's own vector as the NAM-space per-cell statistic, so that the medians and the QC count below
+// can be fed values no kurtosis kernel produces (one rank holding the whole graph: n_global entries, device cell order)
+int cna_load_cell_stat(cna_ctx* c, const double* v, int64_t n) {
+  CHECK_CTX(c);
+  NO_NULL_PENDING(c, "cna_load_cell_stat");
+  AUTO_FINISH(c);
+  if (!c->indptr || !c->stat) CNA_FAIL(CNA_ESTATE, "cna_load_cell_stat before cna_graph_upload");
+  if (c->nranks != 1 || c->local_view || c->n_local != c->n_global)
+    CNA_FAIL(CNA_ESTATE, "cna_load_cell_stat: one rank holding the whole graph only");
+  if (!v) CNA_FAIL(CNA_EINVAL, "cna_load_cell_stat: null pointer");
+  if (n != c->n_global) CNA_FAIL(CNA_EINVAL, "cna_load_cell_stat: expected n_global entries");
+  HIP_TRY(hipMemcpyAsync(c->stat, v, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));      // (the caller's vector may go out of scope)
+  c->stat_space = CNA_MAT_NAM;
+  return 0;
+}
+
 // Exact median of the per-cell statistic (np.median semantics: NaN if any entry is NaN, mean of the
 // two middle values for an even count) by radix select on the device: 8 passes of an 8-bit digit
 // histogram per order statistic, a 2 KB read-back each -- ~0.3 ms instead of the 1-6 ms numpy's

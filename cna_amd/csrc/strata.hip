@@ -189,7 +189,7 @@ __global__ __launch_bounds__(64) void k_st_hist(const double* __restrict__ seg, 
 
 // one wave per bin: the digit in which each of the two ranks falls (lane l holds the digits 4 l .. 4 l + 3, a prefix sum
 // over the lanes finds the one that holds the rank), the histogram left zeroed for the next pass; after the last digit the
-// median = (lower + upper) / 2 as np.median forms it
+// median as np.median forms it: the middle value of an odd count, (lower + upper) / 2 of an even one
 __global__ __launch_bounds__(64) void k_st_pick(unsigned int* __restrict__ hist, SelState* __restrict__ sel,
                                                 const unsigned long long* __restrict__ kept, int shift, double* __restrict__ bin) {
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -222,7 +222,10 @@ __global__ __launch_bounds__(64) void k_st_pick(unsigned int* __restrict__ hist,
         sel[b].rank[r] = rem;
       }
     }
-    if (shift == 0 && lane == 0) bin[(int64_t)b * BS_LD + 3] = (key_value(pre[0]) + key_value(pre[1])) / 2.0;
+    if (shift == 0 && lane == 0) {                 // an odd count: the middle value itself (x + x overflows from DBL_MAX / 2 on)
+      const double lo = key_value(pre[0]), hi = key_value(pre[1]);
+      bin[(int64_t)b * BS_LD + 3] = (kept[b] & 1ull) ? lo : (lo + hi) / 2.0;
+    }
   }
   h[lane] = make_uint4(0u, 0u, 0u, 0u);
   h[64 + lane] = make_uint4(0u, 0u, 0u, 0u);

@@ -502,6 +502,15 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_fetch_cell_stat(self.h, ptr(out), int(n_expected)), 'cna_fetch_cell_stat')
         return self.cells_to_user(out) if nam_space else out
 
+    def load_cell_stat(self, v):
+        """For tests: v (one float64 per cell of the resident graph) becomes the NAM-space per-cell statistic, as it
+        stands -- stat_median() / stat_qc() then work on values of the caller's choosing.  cell_stat() hands the vector
+        back through the device cell order: compare sorted, or undo that with cells_to_device()."""
+        v = _f64(v)
+        if v.ndim != 1:
+            raise ValueError('the per-cell statistic is a vector')
+        check(self.lib.cna_load_cell_stat(self.h, ptr(v), len(v)), 'cna_load_cell_stat')
+
     # ---------------------------------------------------------------- dense diffusion
     def dense_load(self, s_local):
         s_local = _f64(s_local)

@@ -186,6 +186,13 @@ int  cna_fetch_cell_stat(cna_ctx* ctx, double* out, int64_t n_expected);
  * by an exact radix select: NaN if any entry is NaN, mean of the two middle values for an even count
  * (medians of _nam.py:59,94,150) */
 int  cna_stat_median(cna_ctx* ctx, double* median_out);
+/* FOR TESTS.  The analysis never calls this: it exists so that the suite can choose, bit by bit, the vector that
+ * cna_stat_median, cna_stat_qc and cna_fetch_cell_stat work on (the reference's medians and QC count: _nam.py:64-68,
+ * _nam.py:94-96), where the kurtosis kernels only ever leave a narrow band of values.  v[0..n) replaces the NAM-space
+ * per-cell statistic as it stands on the device (device cell order; medians and counts do not depend on the order).
+ * One rank holding the whole graph; n must equal n_global (CNA_EINVAL, as for v = NULL); CNA_ESTATE before
+ * cna_graph_upload, on a sharded context, and while a local-null pass is pending. */
+int  cna_load_cell_stat(cna_ctx* ctx, const double* v, int64_t n);
 
 /* cna.tl.diffuse / diffuse_stepwise on an arbitrary dense cells x m state (_nam.py:21-41):
  * load the local rows, step, fetch the local rows (unscaled state s). */
