@@ -1294,6 +1294,58 @@ class Engine(_order.CellOrder):
                                                                'max', 'vals')]), 'cna_coef_strata')
         return out
 
+    def matrix_to_bins(self, which, codes, W=None, n_bins=None):
+        """Weighted per-bin sums over the rows of the resident NAM (MAT_NAM) or of the working matrix X (MAT_X), on the
+        device (cna_matrix_to_bins): `codes` int32 per cell in the CALLER's order, -1 = cell left out; `W` q x cells
+        float64 in the caller's order (a weight that is zero or not finite leaves the cell out of that column) or None:
+        every weight 1; `n_bins` defaults to the largest code + 1.  The cells are mapped to the matrix' rows here: the
+        device's cell order for the NAM, `x_row_of_cells()` for an X that is a selection (a cell it dropped contributes
+        nothing), the identity for an X from `upload_x` (one code per row).  Returns (sums float64[max(q, 1), n_bins,
+        n_cols], n int64[max(q, 1), n_bins]: the contributing cells).  One rank, replicated view."""
+        if self.nranks != 1 or self.view_local:
+            raise NotImplementedError('matrix_to_bins needs every row of the matrix on this rank (one rank, replicated view)')
+        if which not in (MAT_NAM, MAT_X):
+            raise ValueError('matrix_to_bins: which is MAT_NAM or MAT_X')
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if W is not None:
+            W = _f64(W)
+        selection = which == MAT_X and self._x_is_selection
+        cells = int(self.x_rows_total) if which == MAT_X and not selection else int(self.n)
+        if codes.shape != (cells,):
+            raise ValueError('matrix_to_bins: %s codes for %d cells' % (codes.shape, cells))
+        if W is not None and (W.ndim != 2 or W.shape[1] != cells):
+            raise ValueError('matrix_to_bins: weights %s for %d cells (q x cells)' % (W.shape, cells))
+        if n_bins is None:
+            n_bins = max(int(codes.max(initial=-1)) + 1, 1)
+        if which == MAT_NAM:
+            if self.perm is not None:
+                codes = np.ascontiguousarray(codes[self.perm])
+                W = None if W is None else np.ascontiguousarray(W[:, self.perm])
+        elif selection:
+            xrow = self.x_row_of_cells()
+            has = np.flatnonzero(xrow >= 0)
+            local = np.full(int(self.x_rows_total), -1, dtype=np.int32)
+            local[xrow[has]] = codes[has]
+            if W is not None:
+                Wl = np.zeros((W.shape[0], len(local)))
+                Wl[:, xrow[has]] = W[:, has]
+                W = Wl
+            codes = local
+        return self.matrix_rows_to_bins(which, codes, W, n_bins)
+
+    def matrix_rows_to_bins(self, which, codes, W, n_bins):
+        """cna_matrix_to_bins as it is: `codes` and the columns of `W` (or None) are per LOCAL ROW of the matrix."""
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        W = None if W is None else _f64(W)
+        q = 0 if W is None else int(W.shape[0])
+        n_bins = int(n_bins)
+        n_cols = self.matrix_shape(which)[1]
+        sums = np.empty((max(q, 1), max(n_bins, 0), n_cols))
+        n = np.empty((max(q, 1), max(n_bins, 0)), dtype=np.int64)
+        check(self.lib.cna_matrix_to_bins(self.h, int(which), ptr(codes), ptr(W), q, codes.size, n_bins, ptr(sums), ptr(n)),
+              'cna_matrix_to_bins')
+        return sums, n
+
     def x_generation(self):
         """How often the library has voided the working matrix X so far (cna_x_generation: every producer of X and every
         transition above it, in place or not)."""

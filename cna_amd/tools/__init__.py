@@ -5,6 +5,7 @@ from ._genes import gene_corr
 from ._gene_test import gene_test
 from ._strata import coef_strata
 from ._gene_strata import gene_corr_strata
+from ._nam_strata import nam_strata
 
 __all__ = [
     'association',
@@ -13,6 +14,7 @@ __all__ = [
     'gene_corr_strata',
     'gene_test',
     'nam',
+    'nam_strata',
     'svd_nam',
     'diffuse',
     'diffuse_stepwise',

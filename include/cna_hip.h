@@ -55,6 +55,9 @@ enum {
      exchange of state rows between walk steps (pack + ncclSend/Recv + unpack, on its own stream when it overlaps the step)
      and how long the main stream then STOOD STILL waiting for it (0 when the step's safe rows hid it) */
   CNA_K_HALO_EXCHANGE, CNA_K_HALO_WAIT,
+  /* cna_matrix_to_bins on the expression stream: the counting sort of the rows with its verdict, then the row list, the
+   * sums and the fold (csrc/nam_bins.hip) */
+  CNA_K_MATRIX_BINS_SORT, CNA_K_MATRIX_BINS_SUM,
   CNA_K_COUNT
 };
 
@@ -602,8 +605,8 @@ int  cna_expr_upload_dense(cna_ctx* ctx, const void* x, int64_t n_cells, int64_t
 int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indices, const void* data, int64_t n_cells,
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
- * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata and cna_gene_corr_by: cna_ctx_device_bytes returns to what
- * it was before the upload. */
+ * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by and cna_matrix_to_bins:
+ * cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -720,6 +723,35 @@ int  cna_expr_cross(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, double* 
 /* Counts the times the working matrix X and what is derived from it were voided (every producer of X, every transition
  * above it): a caller that keeps something derived from X (cna_expr_cross' result) may keep it while this stands still. */
 int  cna_x_generation(cna_ctx* ctx, int64_t* gen);
+
+/* ---- the NAM or the working matrix by bin (csrc/nam_bins.hip) ---------------------------------- */
+/* "Working directly with the NAM" (demo/demo.ipynb, section 3.2) and the plot every analysis ends on -- the phenotype against
+ * the abundance of the associated population in each sample -- need sums over the cell axis of the NAM (_nam.py:73), per
+ * cluster and per weight column; the reference takes the NAM to the host for them and aggregates as utils/multisample.py:4-11
+ * aggregates per-cell columns.  Here the matrix stays where it is: one read of it, weights x bins x samples out.
+ *   which     CNA_MAT_NAM or CNA_MAT_X
+ *   codes[r]  the bin of LOCAL ROW r of that matrix (the device's row order, as for cna_fetch_rows and cna_load_cell_stat),
+ *             -1 for a row that is left out; n_rows must equal the rows cna_matrix_shape reports; 1 <= n_bins <= 1024
+ *   W         q x n_rows row-major weights, 0 <= q <= 16, or NULL with q = 0: every weight 1; max(q, 1) x n_bins <= 4096
+ * Row r CONTRIBUTES to weight column j when codes[r] >= 0 and W[j][r] is finite and not zero (q = 0: when codes[r] >= 0).  A
+ * row that does not contribute is not multiplied at all: a zero weight against a NaN entry of the matrix adds nothing.
+ *   sums_out[(j * n_bins + L) * n_cols + s] = sum over the contributing rows r of bin L of W[j][r] * M[r][s], n_cols as
+ *   cna_matrix_shape reports it (the padding up to the leading dimension never appears)
+ *   n_out[j * n_bins + L] = the number of those rows
+ * (one weight column and n_bins rows of each with q = 0).  A bin without contributing rows gives 0; NaN / inf inside the
+ * matrix reach their own (j, bin, column) only.  Sums are float64 in a fixed order (the rows of a bin ascending, cut into
+ * chunks whose partials are added in chunk order; no floating-point atomics): two runs give the same bits.  The product is
+ * fused: sum = fma(w, x, sum), one rounding per row.
+ * CNA_MAT_NAM collects a pending cna_nam_auto_launch verdict and produces a NAM that cna_nam_select_hint's by-product left
+ * lazy, as cna_fetch_rows does.  The matrix is read and left as it is and nothing derived from it is kept.  Runs on the
+ * expression stream with grow-only buffers of its own (freed by cna_expr_drop), needs no resident expression matrix, waits
+ * there, through an event, for what the main stream has queued that produces the matrix, and returns only after its own
+ * stream has drained, so a later producer finds the read finished.
+ * CNA_ESTATE: the matrix is not available, or the context has a communicator (the rows of other ranks are elsewhere).
+ * CNA_EINVAL, with nothing written: which, q, n_bins or n_rows out of range, or a code outside [-1, n_bins) -- found on the
+ * device before any sum is formed. */
+int  cna_matrix_to_bins(cna_ctx* ctx, int which, const int32_t* codes, const double* W, int q, int64_t n_rows, int n_bins,
+                        double* sums_out, int64_t* n_out);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
