@@ -1346,6 +1346,30 @@ class Engine(_order.CellOrder):
               'cna_matrix_to_bins')
         return sums, n
 
+    def enrichment_extremes(self, R, set_ptr, set_genes, weight):
+        """The running-sum extremes of gene set enrichment for every set under every row of `R` (n_cols x genes float64,
+        the observed correlations first, then one row per null column; a non-finite entry leaves the gene out of that
+        row), on the device (cna_enrichment_extremes): `set_ptr` n_sets + 1 offsets into `set_genes`, the members' gene
+        indices, ascending and distinct inside a set; `weight` 0, 1 or 2, the exponent of |r|.  Returns (up float64[n_cols,
+        n_sets], down likewise, size int32[n_cols, n_sets]: the set's valid members, valid int32[n_cols]: the row's valid
+        genes); up and down are NaN where the set has no valid member, every valid gene, or no weight.  Needs no graph
+        and no resident expression matrix; `drop_expression` frees its device buffers."""
+        R = _f64(R)
+        set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int64)
+        set_genes = np.ascontiguousarray(set_genes, dtype=np.int32)
+        if R.ndim != 2 or set_ptr.ndim != 1 or set_genes.ndim != 1 or len(set_ptr) < 2 or set_ptr[-1] != len(set_genes):
+            raise ValueError('enrichment_extremes: R is n_cols x genes, set_ptr holds n_sets + 1 offsets that end at len(set_genes)')
+        n_cols, n_genes = R.shape
+        n_sets = len(set_ptr) - 1
+        up, down = np.empty((n_cols, n_sets)), np.empty((n_cols, n_sets))
+        size = np.empty((n_cols, n_sets), dtype=np.int32)
+        valid = np.empty(n_cols, dtype=np.int32)
+        if not len(set_genes):
+            set_genes = np.zeros(1, dtype=np.int32)         # a pointer the library can take; no offset reaches it
+        check(self.lib.cna_enrichment_extremes(self.h, ptr(R), n_cols, n_genes, ptr(set_ptr), ptr(set_genes), n_sets, int(weight),
+                                               ptr(up), ptr(down), ptr(size), ptr(valid)), 'cna_enrichment_extremes')
+        return up, down, size, valid
+
     def x_generation(self):
         """How often the library has voided the working matrix X so far (cna_x_generation: every producer of X and every
         transition above it, in place or not)."""

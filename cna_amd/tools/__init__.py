@@ -6,12 +6,15 @@ from ._gene_test import gene_test
 from ._strata import coef_strata
 from ._gene_strata import gene_corr_strata
 from ._nam_strata import nam_strata
+from ._gene_sets import gene_set_enrich, gene_set_test
 
 __all__ = [
     'association',
     'coef_strata',
     'gene_corr',
     'gene_corr_strata',
+    'gene_set_enrich',
+    'gene_set_test',
     'gene_test',
     'nam',
     'nam_strata',

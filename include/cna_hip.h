@@ -58,6 +58,9 @@ enum {
   /* cna_matrix_to_bins on the expression stream: the counting sort of the rows with its verdict, then the row list, the
    * sums and the fold (csrc/nam_bins.hip) */
   CNA_K_MATRIX_BINS_SORT, CNA_K_MATRIX_BINS_SUM,
+  /* cna_enrichment_extremes on the expression stream: the place of every gene in every column, then the running-sum
+   * extremes of every (column, set) (csrc/enrich.hip) */
+  CNA_K_ENRICH_POSITIONS, CNA_K_ENRICH_EXTREMES,
   CNA_K_COUNT
 };
 
@@ -605,7 +608,8 @@ int  cna_expr_upload_dense(cna_ctx* ctx, const void* x, int64_t n_cells, int64_t
 int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indices, const void* data, int64_t n_cells,
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
- * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by and cna_matrix_to_bins:
+ * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins and
+ * cna_enrichment_extremes:
  * cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
@@ -752,6 +756,41 @@ int  cna_x_generation(cna_ctx* ctx, int64_t* gen);
  * device before any sum is formed. */
 int  cna_matrix_to_bins(cna_ctx* ctx, int which, const int32_t* codes, const double* W, int q, int64_t n_rows, int n_bins,
                         double* sums_out, int64_t* n_out);
+
+/* ---- gene set enrichment of the gene correlations (csrc/enrich.hip) ---------------------------- */
+/* demo/demo.ipynb, section 1.5, ends the per-gene correlations to the neighbourhood coefficient with "they could be further
+ * analyzed using techniques like gene set enrichment analysis".  This is that analysis' cell-free core, for the variant
+ * that permutes the phenotype: the extremes of the running sum of every gene set under every column of [r | null_r], the
+ * null columns being the correlations under the association's own conditional permutations (_association.py:94-99, as
+ * cna.tl.gene_test forms them).
+ *   R          n_cols x n_genes row-major, one row per phenotype column (the observed r first); 1 <= n_cols <= 4096,
+ *              1 <= n_genes < 2^31
+ *   set_ptr    n_sets + 1 offsets into set_genes, starting at 0, not falling; 1 <= n_sets <= 2^20, at most 4096 members per
+ *              set, fewer than 2^31 in all
+ *   set_genes  the members' gene indices, in [0, n_genes) and strictly ascending inside a set
+ *   weight     0, 1 or 2: the exponent p of w = |r|^p, evaluated as 1, fabs(r), r * r (a product rounded on its own).  Other
+ *              exponents are refused: pow rounds differently in libm and on the device
+ * For column c a gene is VALID when R[c][g] is finite; valid_out[c] = Gv, their number.  The position of a valid gene is
+ *   pos(g) = #{valid h : r_h > r_g} + #{valid h < g : r_h == r_g}
+ * -- its place in np.argsort(-r, kind='stable') over the valid genes; +0.0 and -0.0 tie.  For set s take its valid members in
+ * order of position, j = 1 .. k, with w_j their weight, S_j = w_1 + ... + w_j, N_R = S_k and m_j = pos_j - (j - 1) the misses
+ * before hit j:
+ *   up_out[c * n_sets + s]   = max_j  S_j / N_R - (double)m_j / (double)(Gv - k)
+ *   down_out[c * n_sets + s] = min_j  S_(j-1) / N_R - (double)m_j / (double)(Gv - k)
+ *   size_out[c * n_sets + s] = k
+ * two divisions and one subtraction each, in exactly this form.  Both are NaN when k == 0, k == Gv or N_R == 0; otherwise
+ * up >= 0 >= down.  The enrichment score, ES = up if up >= -down else down, is left to the caller: a near-tie of the two
+ * extremes cannot turn one rounding into a sign flip here, and both tails are available.
+ * The positions are integer counts over all pairs of genes of a column (exact, ties by construction); S_j is added in a
+ * fixed order and the extremes are folded by fmax / fmin; no floating-point atomics: two runs give the same bits.
+ * Like cna_coef_strata it needs no graph and no resident expression matrix and changes no other state; it runs on the
+ * expression stream with grow-only buffers of its own (freed by cna_expr_drop; 12 bytes per entry of R) and returns after that
+ * stream has drained.
+ * CNA_EINVAL, with nothing written: a limit above violated, a weight other than 0, 1, 2, or a member out of range or out of
+ * order -- found on the device before any sum is formed. */
+int  cna_enrichment_extremes(cna_ctx* ctx, const double* R, int64_t n_cols, int64_t n_genes, const int64_t* set_ptr,
+                             const int32_t* set_genes, int n_sets, int weight, double* up_out, double* down_out,
+                             int32_t* size_out, int32_t* valid_out);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
