@@ -2,12 +2,14 @@
 // work on the expression stream, one file each: cna_gene_corr (expr_corr.hip), cna_expr_to_bins (expr_bins.hip),
 // cna_expr_cross (expr_cross.hip), cna_coef_strata (strata.hip), cna_gene_corr_by (expr_corr_by.hip), cna_matrix_to_bins
 // (nam_bins.hip: the NAM or X by bin, on this stream with this sort), cna_enrichment_extremes (enrich.hip: no matrix at all,
-// this stream and these buffers).  What two of them need is here once:
+// this stream and these buffers), cna_expr_cross_by (expr_cross_by.hip) and cna_gram_by (gram_by.hip: X alone).  What two of
+// them need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared
 //   ExprState       the resident matrix, the stream, and one slot of work buffers per entry point
 //   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins and cna_gene_corr_by, value
 //                   segments of cna_coef_strata): one count kernel, one fill kernel, one host half; CellListOf
 //   gene_tiles      the walk over tiles of whole genes of the gene-major kernels
+//   xrow_check      the verdict on a map cells -> rows of X (cna_expr_cross and the two entries by level)
 //   with_bool / with_width, fetch_results, finite_d, wave_min / wave_max
 // Templates are instantiated where they are used; nothing here needs relocatable device code.
 #pragma once
@@ -51,7 +53,8 @@ struct ScopedBufs : BufSet {
 };
 
 // ------------------------------------------------------------------ state (cna_ctx::expr)
-enum ExprUser { EXPR_CORR, EXPR_BINS, EXPR_CROSS, EXPR_STRATA, EXPR_CORR_BY, EXPR_MAT_BINS, EXPR_ENRICH, EXPR_USERS };
+enum ExprUser { EXPR_CORR, EXPR_BINS, EXPR_CROSS, EXPR_STRATA, EXPR_CORR_BY, EXPR_MAT_BINS, EXPR_ENRICH, EXPR_CROSS_BY,
+                EXPR_GRAM_BY, EXPR_USERS };
 
 struct ExprState {
   hipStream_t st = nullptr;
@@ -98,6 +101,11 @@ struct HostCopy {
   size_t bytes;
 };
 int fetch_results(hipStream_t st, const char* who, std::initializer_list<HostCopy> copies);
+
+// The verdict on a map cells -> rows of X (xrow_dev: n entries on the device; expr_cross.hip, k_xc_check): CNA_EINVAL under
+// who's name for a value outside [-1, nx) or a row named twice, before any sum is formed; *m = the cells with a row
+int xrow_check(cna_ctx* c, hipStream_t st, const int64_t* xrow_dev, int64_t n, int64_t nx, Buf& seen, Buf& flag,
+               const char* who, int64_t* m);
 
 // ------------------------------------------------------------------ run-time value -> template argument
 // f(std::true_type / std::false_type); f(std::integral_constant<int, W>) for the least W of 1, 2, 4, 8, 16 that holds w

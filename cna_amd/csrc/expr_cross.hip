@@ -284,6 +284,26 @@ int xc_sparse(cna_ctx* c, ExprState* s, CrossWork* w, const double* Xw, int ldx,
 
 }  // namespace
 
+// expr.h: the verdict on a map cells -> rows of X, for every entry that takes one
+int xrow_check(cna_ctx* c, hipStream_t st, const int64_t* xrow_dev, int64_t n, int64_t nx, Buf& seen, Buf& flag,
+               const char* who, int64_t* m) {
+  CNA_TRY(buf_need(c, st, seen, 4 * std::max<int64_t>(1, nx)));
+  CNA_TRY(buf_need(c, st, flag, 256));
+  HIP_TRY(hipMemsetAsync(seen.p, 0, (size_t)(4 * std::max<int64_t>(1, nx)), st));
+  HIP_TRY(hipMemsetAsync(flag.p, 0, 16, st));
+  hipLaunchKernelGGL(k_xc_check, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, xrow_dev, n, nx,
+                     seen.as<unsigned int>(), flag.as<int>(), (unsigned long long*)((char*)flag.p + 8));
+  HIP_TRY(hipGetLastError());
+  int64_t verdict[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(verdict, flag.p, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int bad = (int)(verdict[0] & 0xffffffffll);
+  if (bad & 1) CNA_FAIL(CNA_EINVAL, std::string(who) + ": an xrow lies outside [-1, rows of X)");
+  if (bad & 2) CNA_FAIL(CNA_EINVAL, std::string(who) + ": two cells name the same row of X");
+  *m = verdict[1];
+  return 0;
+}
+
 extern "C" int cna_expr_cross(cna_ctx* c, const int64_t* xrow, int64_t n_cells, double* W_out, double* rho_out, double* sx_out,
                    double* sxx_out, int64_t* m_out) {
   CHECK_CTX(c);
@@ -303,23 +323,11 @@ extern "C" int cna_expr_cross(cna_ctx* c, const int64_t* xrow, int64_t n_cells, 
   CrossWork* w = expr_work<CrossWork>(s, EXPR_CROSS);
   const int64_t n_out = G * Nx + Nx + 2 * G;
   CNA_TRY(buf_need(c, s->st, w->xrow, 8 * n));
-  CNA_TRY(buf_need(c, s->st, w->xseen, 4 * std::max<int64_t>(1, nx)));
-  CNA_TRY(buf_need(c, s->st, w->flag, 256));
   CNA_TRY(buf_need(c, s->st, w->xout, 8 * n_out));
   HIP_TRY(hipMemcpyAsync(w->xrow.p, xrow, (size_t)(8 * n), hipMemcpyHostToDevice, s->st));
-  HIP_TRY(hipMemsetAsync(w->xseen.p, 0, (size_t)(4 * std::max<int64_t>(1, nx)), s->st));
-  HIP_TRY(hipMemsetAsync(w->flag.p, 0, 16, s->st));
-  hipLaunchKernelGGL(k_xc_check, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, s->st,
-                     (const int64_t*)w->xrow.p, n, nx, (unsigned int*)w->xseen.p, (int*)w->flag.p,
-                     (unsigned long long*)((char*)w->flag.p + 8));
-  HIP_TRY(hipGetLastError());
   // xrow is judged before any sum is formed (and before X is touched)
-  int64_t verdict[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(verdict, w->flag.p, 16, hipMemcpyDeviceToHost, s->st));
-  HIP_TRY(hipStreamSynchronize(s->st));
-  const int bad = (int)(verdict[0] & 0xffffffffll);
-  if (bad & 1) CNA_FAIL(CNA_EINVAL, "cna_expr_cross: an xrow lies outside [-1, rows of X)");
-  if (bad & 2) CNA_FAIL(CNA_EINVAL, "cna_expr_cross: two cells name the same row of X");
+  int64_t m = 0;
+  CNA_TRY(xrow_check(c, s->st, w->xrow.as<const int64_t>(), n, nx, w->xseen, w->flag, "cna_expr_cross", &m));
   // whatever the main stream has queued that produces X comes first (an event, no host sync).  The other direction needs
   // nothing: this entry returns only after the expression stream has drained, so a later producer of X finds the read done
   HIP_TRY(hipEventRecord(s->x_ready, c->stream));
@@ -351,6 +359,6 @@ extern "C" int cna_expr_cross(cna_ctx* c, const int64_t* xrow, int64_t n_cells, 
   std::memcpy(rho_out, host.data() + G * Nx, 8 * (size_t)Nx);
   std::memcpy(sx_out, host.data() + G * Nx + Nx, 8 * (size_t)G);
   std::memcpy(sxx_out, host.data() + G * Nx + Nx + G, 8 * (size_t)G);
-  *m_out = verdict[1];
+  *m_out = m;
   return 0;
 }

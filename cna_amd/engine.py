@@ -55,6 +55,8 @@ class Engine(_order.CellOrder):
         self._expr_key = self._expr_hash = self._expr_ref = self._expr_pinned = None
         self._cross_memo = None     # (key, content signature, result) of the last expr_cross
         self.cross_launches = 0     # cna_expr_cross calls so far (a memo hit launches nothing)
+        self._cross_by_memo = None  # (key, content signature, codes digest, n_bins, result, extra) of the last expr_cross_by
+        self.cross_by_launches = 0  # expr_cross_by calls that went to the device (a memo hit launches nothing)
         self._host_threads = _order.usable_cpus(8)
         self._colsum_w = None
         self._codes_token = self._codes_graph = None
@@ -1169,6 +1171,7 @@ class Engine(_order.CellOrder):
         """Forget the resident expression matrix and free its device memory: the next call uploads afresh."""
         self._expr_key = self._expr_hash = self._expr_ref = None
         self._cross_memo = None
+        self._cross_by_memo = None
         check(self.lib.cna_expr_drop(self.h), 'cna_expr_drop')
 
     def ensure_expression(self, X):
@@ -1425,6 +1428,132 @@ class Engine(_order.CellOrder):
     def cross_extra(self):
         """The dict that goes with the current expr_cross memo (empty after every launch, gone with the memo)."""
         return {} if self._cross_memo is None else self._cross_memo[3]
+
+    CROSS_BY_HOST_BYTES = 1 << 30      # the whole W of expr_cross_by that is taken in one call and kept
+
+    def expr_cross_by_raw(self, xrow, codes, n_bins, bin0=0, nb=None):
+        """(W float64[nb, genes, samples], sx, sxx float64[nb, genes], m int64[nb]) for the levels [bin0, bin0 + nb) of
+        `codes` (int32 per cell, -1 = cell left out), `xrow` the row of X of every cell.  A dense resident matrix:
+        cna_expr_cross_by, one pass for all levels.  Gene-major lists: one cna_expr_cross per level with xrow masked to
+        that level -- the one-pass kernel for that form lost its measurement at 1M cells x 100 samples
+        (profiles/kbench_gene_test_strata.txt) and is not in the library; the codes are checked here, and a refusal is a
+        CnaHipError in either form."""
+        xrow = np.ascontiguousarray(xrow, dtype=np.int64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if xrow.ndim != 1 or codes.shape != xrow.shape:
+            raise ValueError('expr_cross_by: xrow and codes must be 1-D and of one length')
+        n_bins, bin0 = int(n_bins), int(bin0)
+        nb = n_bins - bin0 if nb is None else int(nb)
+        info = self.expression_shape()
+        g = info['n_genes']
+        cols = self.matrix_shape(MAT_X)[1] if info['format'] != 'none' else 0
+        k = max(nb, 0)
+        W, sx, sxx, m = np.empty((k, g, cols)), np.empty((k, g)), np.empty((k, g)), np.empty(k, dtype=np.int64)
+        if info['format'] == 'gene-major':
+            # the checks cna_expr_cross_by makes, under the error type it raises through check()
+            if not 1 <= n_bins <= 1024 or bin0 < 0 or nb < 1 or bin0 + nb > n_bins:
+                raise _ffi.CnaHipError('expr_cross_by failed: 1 <= n_bins <= 1024 and the levels [bin0, bin0 + nb) must lie in '
+                                       '[0, n_bins), nb >= 1')
+            if len(codes) and (codes.min() < -1 or codes.max() >= n_bins):
+                raise _ffi.CnaHipError('expr_cross_by failed: a code lies outside [-1, n_bins)')
+            for l in range(nb):
+                W[l], _, sx[l], sxx[l], m[l] = self.expr_cross(xrow=np.where(codes == bin0 + l, xrow, -1))
+            return W, sx, sxx, m
+        check(self.lib.cna_expr_cross_by(self.h, ptr(xrow), ptr(codes), len(xrow), n_bins, bin0, nb, ptr(W), ptr(sx), ptr(sxx),
+                                         ptr(m)), 'cna_expr_cross_by')
+        return W, sx, sxx, m
+
+    def gram_by(self, xrow, codes, n_bins):
+        """cna_gram_by: (Gamma float64[n_bins, samples, samples], m int64[n_bins]), Gamma[l] = X_l^T X_l over the rows
+        xrow[i] >= 0 of the working matrix X of the cells with codes[i] == l.  Needs no resident expression matrix."""
+        xrow = np.ascontiguousarray(xrow, dtype=np.int64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if xrow.ndim != 1 or codes.shape != xrow.shape:
+            raise ValueError('gram_by: xrow and codes must be 1-D and of one length')
+        n_bins = int(n_bins)
+        cols = self.matrix_shape(MAT_X)[1]
+        k = max(n_bins, 0)
+        Gm, m = np.empty((k, cols, cols)), np.empty(k, dtype=np.int64)
+        check(self.lib.cna_gram_by(self.h, ptr(xrow), ptr(codes), len(xrow), n_bins, ptr(Gm), ptr(m)), 'cna_gram_by')
+        return Gm, m
+
+    def expr_cross_by(self, codes, n_bins, bins=None, content=None, xrow=None):
+        """`expr_cross` inside every level of a clustering: (W, rho, sx, sxx, m, Gamma) for the levels `bins` (default: all
+        `n_bins`) of `codes` (int32 per cell in the caller's order, -1 = cell left out), over the cells of each level
+        that have a row in X: W float64[levels, genes, samples] = E_l^T X_l (`expr_cross_by_raw`), rho float64[levels,
+        samples] the column sums of X_l (`matrix_rows_to_bins(MAT_X, ...)`), sx / sxx float64[levels, genes], m
+        int64[levels] the cells, Gamma float64[levels, samples, samples] = X_l^T X_l (cna_gram_by).  One rank, replicated
+        view.
+
+        Memo: beside `expr_cross`'s and under the same key (uploads of the expression matrix, x_epoch, the library's X
+        generation) plus a digest of the codes and n_bins; carried over to a new key under an equal `content`, as there;
+        void wherever that memo is.  `cross_by_launches` counts the calls that went to the device, `cross_by_extra()` is
+        the dict that lives and dies with the memo.  An explicit `xrow` neither reads nor writes the memo.
+
+        When W for all n_bins levels (levels x genes x samples x 8 bytes) or Gamma does not fit 1 GiB of host memory, the
+        method works in groups of levels -- the requested ones only -- and keeps no memo: every such call passes over the
+        expression matrix once per group."""
+        if self.nranks != 1 or self.view_local:
+            raise NotImplementedError('expr_cross_by needs every row of X on this rank (one rank, replicated view)')
+        import hashlib
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        n_bins = int(n_bins)
+        info = self.expression_shape()
+        resident = info['format'] != 'none'
+        key = (info['uploads'] if resident else None, self.x_epoch, self.x_generation())
+        digest = (hashlib.blake2b(codes.view(np.uint8).reshape(-1), digest_size=16).hexdigest(), n_bins)
+        sel = None if bins is None else np.asarray(bins, dtype=np.int64).reshape(-1)
+        if sel is not None and len(sel) and (sel.min() < 0 or sel.max() >= n_bins):
+            raise ValueError('expr_cross_by: bins must lie in [0, n_bins)')
+
+        def pick(out):
+            return out if sel is None else tuple(a[sel] for a in out)
+        memo = self._cross_by_memo
+        if memo is not None and key[0] is not None and xrow is None and memo[2] == digest:
+            if memo[0] == key:
+                return pick(memo[4])
+            if content is not None and memo[1] == content and memo[0][0] == key[0]:
+                self._cross_by_memo = (key, content) + memo[2:]
+                return pick(memo[4])
+        g = info['n_genes']
+        cols = self.matrix_shape(MAT_X)[1] if resident else 0
+        explicit = xrow is not None
+        xrow = np.ascontiguousarray(xrow if explicit else self.x_row_of_cells(), dtype=np.int64)
+
+        def take(cd, k):
+            """the k levels of the codes cd, W and Gamma each in groups that fit"""
+            step = max(1, self.CROSS_BY_HOST_BYTES // max(1, 8 * g * cols))
+            parts = [self.expr_cross_by_raw(xrow, cd, k, b0, min(step, k - b0)) for b0 in range(0, k, step)]
+            W, sx, sxx, m = (np.concatenate([p_[j] for p_ in parts]) if len(parts) > 1 else parts[0][j] for j in range(4))
+            gstep = max(1, self.CROSS_BY_HOST_BYTES // max(1, 8 * cols * cols))
+            grams = [self.gram_by(xrow, np.where((cd >= b0) & (cd < b0 + gstep), cd - b0, -1), min(gstep, k - b0))[0]
+                     for b0 in range(0, k, gstep)]
+            Gamma = np.concatenate(grams) if len(grams) > 1 else grams[0]
+            has = np.flatnonzero((xrow >= 0) & (xrow < int(self.x_rows_total)))
+            local = np.full(int(self.x_rows_total), -1, dtype=np.int32)
+            local[xrow[has]] = cd[has]
+            rho = self.matrix_rows_to_bins(MAT_X, local, None, k)[0][0]
+            self.cross_by_launches += 1                               # counted once nothing has been refused
+            return W, rho, sx, sxx, m, Gamma
+        fits = 8 * n_bins * g * cols <= self.CROSS_BY_HOST_BYTES and 8 * n_bins * cols * cols <= self.CROSS_BY_HOST_BYTES
+        if not fits and n_bins >= 1:
+            want = np.arange(n_bins) if sel is None else sel
+            lut = np.full(n_bins + 1, -1, dtype=np.int32)            # the last entry serves the code -1
+            lut[want] = np.arange(len(want), dtype=np.int32)
+            ok = (codes >= -1) & (codes < n_bins)
+            self._cross_by_memo = None
+            return take(np.where(ok, lut[np.where(ok, codes, -1)], codes).astype(np.int32), len(want))
+        out = take(codes, n_bins)
+        if explicit:
+            return pick(out)
+        for a in out:
+            a.setflags(write=False)
+        self._cross_by_memo = (key, content, digest, n_bins, out, {})
+        return pick(out)
+
+    def cross_by_extra(self):
+        """The dict that goes with the current expr_cross_by memo (empty after every launch, gone with the memo)."""
+        return {} if self._cross_by_memo is None else self._cross_by_memo[5]
 
     # ---------------------------------------------------------------- synthetic inputs
     def knn_graph(self, X, k):

@@ -5,6 +5,7 @@ from ._genes import gene_corr
 from ._gene_test import gene_test
 from ._strata import coef_strata
 from ._gene_strata import gene_corr_strata
+from ._gene_test_strata import gene_test_strata
 from ._nam_strata import nam_strata
 from ._gene_sets import gene_set_enrich, gene_set_test
 
@@ -16,6 +17,7 @@ __all__ = [
     'gene_set_enrich',
     'gene_set_test',
     'gene_test',
+    'gene_test_strata',
     'nam',
     'nam_strata',
     'svd_nam',

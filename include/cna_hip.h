@@ -61,6 +61,10 @@ enum {
   /* cna_enrichment_extremes on the expression stream: the place of every gene in every column, then the running-sum
    * extremes of every (column, set) (csrc/enrich.hip) */
   CNA_K_ENRICH_POSITIONS, CNA_K_ENRICH_EXTREMES,
+  /* cna_expr_cross_by and cna_gram_by on the expression stream: the fill of the level-sorted list, the sums over the cells
+   * and their folds; the checks of xrow and the sort's count before them are outside (csrc/expr_cross_by.hip,
+   * csrc/gram_by.hip) */
+  CNA_K_EXPR_CROSS_BY, CNA_K_GRAM_BY,
   CNA_K_COUNT
 };
 
@@ -608,8 +612,8 @@ int  cna_expr_upload_dense(cna_ctx* ctx, const void* x, int64_t n_cells, int64_t
 int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indices, const void* data, int64_t n_cells,
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
- * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins and
- * cna_enrichment_extremes:
+ * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
+ * cna_enrichment_extremes, cna_expr_cross_by and cna_gram_by:
  * cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
@@ -727,6 +731,41 @@ int  cna_expr_cross(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, double* 
 /* Counts the times the working matrix X and what is derived from it were voided (every producer of X, every transition
  * above it): a caller that keeps something derived from X (cna_expr_cross' result) may keep it while this stands still. */
 int  cna_x_generation(cna_ctx* ctx, int64_t* gen);
+
+/* ---- the same inside every level of a clustering (csrc/expr_cross_by.hip, csrc/gram_by.hip) ---- */
+/* What cna.tl.gene_test_strata needs from the cells: the sums of cna_expr_cross over the cells of one level (cluster) at a
+ * time, so that the correlation of gene g with the null coefficient c_p = X^T z_p / N (_association.py:94-99) inside level l
+ * -- the question cna.pl.violinplot(d, 'leiden', key='coef') (plotting/_strat.py:21-29) raises -- is sample-space algebra:
+ *   sum_{i in C_l} x[i,g] c_p[i] = (W_l[g] . z_p) / N,   sum c_p[i] = (rho_l . z_p) / N,   sum c_p[i]^2 = z_p^T Gamma_l z_p / N^2
+ * codes[i] is the level of cell i (CALLER's cell order), -1 for a cell that is left out, 1 <= n_bins <= 1024; xrow[i] its
+ * row of X as for cna_expr_cross.  A cell takes part in level codes[i] when codes[i] >= 0 and xrow[i] >= 0 (C_l).
+ *
+ * cna_expr_cross_by, for the levels [bin0, bin0 + nb) of n_bins, l = level - bin0:
+ *   W_out[(l * n_genes + g) * n_cols + s] = sum over C_level of x[i,g] * X[xrow[i]][s]
+ *   sx_out[l * n_genes + g], sxx_out[l * n_genes + g] = their sums of x[i,g] and x[i,g]^2;  m_out[l] = |C_level|
+ * in one pass over the resident DENSE matrix; rho_l is cna_matrix_to_bins(CNA_MAT_X).  n_cells must equal the resident
+ * matrix' cells.  A gene-major resident matrix is refused with CNA_ESTATE: a one-pass kernel for that form was measured
+ * slower than one cna_expr_cross per level with xrow masked to the level (profiles/kbench_gene_test_strata.txt) and is not
+ * in the library; Engine.expr_cross_by takes that route for it.
+ *
+ * cna_gram_by, for every level: gram_out[(l * n_cols + a) * n_cols + b] = sum over C_l of X[xrow[i]][a] * X[xrow[i]][b]
+ * (symmetric: the upper triangle is computed on the f64 matrix cores and mirrored; all levels together do the flops of one
+ * cna_gram, the NAM.dot(NAM.T) of _nam.py:105), m_out[l] = |C_l|.  It needs no resident expression matrix; 1 <= n_cells <
+ * 2^31.  CNA_EINVAL when n_bins x n_cols^2 x 8 bytes exceed 1 GiB: take the levels in groups (cells of other levels -1).
+ *
+ * Both check xrow (as cna_expr_cross does) and the codes on the device before any sum is formed: CNA_EINVAL, with nothing
+ * written, for an xrow outside [-1, rows of X), a row of X named twice, a code outside [-1, n_bins), or a count out of
+ * range (n_bins, bin0, nb, n_cells, n_cols <= 1024) -- those before anything is queued.  CNA_ESTATE: no X, a context with a
+ * communicator (the rows of other ranks are elsewhere), and for cna_expr_cross_by no resident dense expression matrix.
+ * Sums are float64 in a fixed order (the cells of a level ascending, cut into chunks whose partials are added in chunk order;
+ * no floating-point atomics): two runs give the same bits.  NaN / inf inside the expression matrix reach their own (level,
+ * gene) only.  Both run on the expression stream with grow-only buffers of their own (freed by cna_expr_drop), read X and leave it
+ * as it is, wait there through an event for what the main stream has queued that produces X, and return only after their
+ * own stream has drained. */
+int  cna_expr_cross_by(cna_ctx* ctx, const int64_t* xrow, const int32_t* codes, int64_t n_cells, int n_bins, int bin0, int nb,
+                       double* W_out, double* sx_out, double* sxx_out, int64_t* m_out);
+int  cna_gram_by(cna_ctx* ctx, const int64_t* xrow, const int32_t* codes, int64_t n_cells, int n_bins, double* gram_out,
+                 int64_t* m_out);
 
 /* ---- the NAM or the working matrix by bin (csrc/nam_bins.hip) ---------------------------------- */
 /* "Working directly with the NAM" (demo/demo.ipynb, section 3.2) and the plot every analysis ends on -- the phenotype against
