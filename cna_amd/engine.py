@@ -19,6 +19,61 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def array_digest(a):
+    """128-bit content hash of an array's bytes, as hex."""
+    import hashlib
+    return hashlib.blake2b(np.ascontiguousarray(a).view(np.uint8).reshape(-1), digest_size=16).hexdigest()
+
+
+def _rows_of_x(xrow, n_rows, codes, W=None):
+    """Caller-order `codes` (int32 per cell) and the columns of `W` (q x cells, or None) scattered onto the n_rows rows of
+    X: cell i goes to row xrow[i]; a cell without a row is left out, a row without a cell gets code -1 and weight 0."""
+    has = np.flatnonzero((xrow >= 0) & (xrow < n_rows))
+    local = np.full(n_rows, -1, dtype=np.int32)
+    local[xrow[has]] = codes[has]
+    if W is None:
+        return local, None
+    Wl = np.zeros((W.shape[0], n_rows))
+    Wl[:, xrow[has]] = W[:, has]
+    return local, Wl
+
+
+class _Memo:
+    """What expr_cross / expr_cross_by keep of their last launch: `key` = _x_key then, `content` the caller's word for what
+    X was made from, `tag` what else a hit needs equal (expr_cross_by: the codes' digest and n_bins), `result`, and `extra`,
+    a dict for what else a caller derives from the same inputs."""
+    __slots__ = ('key', 'content', 'tag', 'result', 'extra')
+
+    def __init__(self, key, content, tag, result):
+        self.key, self.content, self.tag, self.result, self.extra = key, content, tag, result, {}
+
+
+def _x_key(engine, info):
+    """(uploads of the expression matrix `info` describes, or None without one; x_epoch; the library's X generation)"""
+    return (info['uploads'] if info['format'] != 'none' else None, engine.x_epoch, engine.x_generation())
+
+
+def _memo_lookup(memo, key, content, tag):
+    """`memo` when it serves a call under (key, content, tag), else None.  An equal key and tag: a hit, whatever the content.
+    A moved key: a hit only under the same upload, an equal tag and an equal content that is not None -- the entry is carried
+    over, re-keyed, its extra with it."""
+    if memo is None or key[0] is None or memo.tag != tag:
+        return None
+    if memo.key != key:
+        if content is None or memo.content != content or memo.key[0] != key[0]:
+            return None
+        memo.key = key
+    return memo
+
+
+def _memo_store(key, content, tag, result):
+    """A fresh entry (empty extra) for `result`, whose arrays become read-only."""
+    for a in result:
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return _Memo(key, content, tag, result)
+
+
 class Engine(_order.CellOrder):
     def __init__(self, device=None, rank=0, nranks=1, unique_id=None, shm=None):
         """unique_id: RCCL id from rank 0 (one GPU per rank).  shm: (segment name, slot bytes) selects
@@ -53,9 +108,9 @@ class Engine(_order.CellOrder):
         self._graph_ref = None
         self._pinned = None
         self._expr_key = self._expr_hash = self._expr_ref = self._expr_pinned = None
-        self._cross_memo = None     # (key, content signature, result) of the last expr_cross
+        self._cross_memo = None     # the _Memo of the last expr_cross; None voids it
         self.cross_launches = 0     # cna_expr_cross calls so far (a memo hit launches nothing)
-        self._cross_by_memo = None  # (key, content signature, codes digest, n_bins, result, extra) of the last expr_cross_by
+        self._cross_by_memo = None  # the _Memo of the last expr_cross_by, its tag (codes digest, n_bins); None voids it
         self.cross_by_launches = 0  # expr_cross_by calls that went to the device (a memo hit launches nothing)
         self._host_threads = _order.usable_cpus(8)
         self._colsum_w = None
@@ -1325,15 +1380,7 @@ class Engine(_order.CellOrder):
                 codes = np.ascontiguousarray(codes[self.perm])
                 W = None if W is None else np.ascontiguousarray(W[:, self.perm])
         elif selection:
-            xrow = self.x_row_of_cells()
-            has = np.flatnonzero(xrow >= 0)
-            local = np.full(int(self.x_rows_total), -1, dtype=np.int32)
-            local[xrow[has]] = codes[has]
-            if W is not None:
-                Wl = np.zeros((W.shape[0], len(local)))
-                Wl[:, xrow[has]] = W[:, has]
-                W = Wl
-            codes = local
+            codes, W = _rows_of_x(self.x_row_of_cells(), int(self.x_rows_total), codes, W)
         return self.matrix_rows_to_bins(which, codes, W, n_bins)
 
     def matrix_rows_to_bins(self, which, codes, W, n_bins):
@@ -1399,14 +1446,10 @@ class Engine(_order.CellOrder):
         if self.nranks != 1 or self.view_local:
             raise NotImplementedError('expr_cross needs every row of X on this rank (one rank, replicated view)')
         info = self.expression_shape()
-        key = (info['uploads'] if info['format'] != 'none' else None, self.x_epoch, self.x_generation())
-        memo = self._cross_memo
-        if memo is not None and key[0] is not None and xrow is None:
-            if memo[0] == key:
-                return memo[2]
-            if content is not None and memo[1] == content and memo[0][0] == key[0]:
-                self._cross_memo = (key, content, memo[2], memo[3])
-                return memo[2]
+        key = _x_key(self, info)
+        memo = None if xrow is not None else _memo_lookup(self._cross_memo, key, content, None)
+        if memo is not None:
+            return memo.result
         g = info['n_genes']
         cols = self.matrix_shape(MAT_X)[1] if info['format'] != 'none' else 0
         explicit = xrow is not None
@@ -1418,16 +1461,13 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_expr_cross(self.h, ptr(xrow), len(xrow), ptr(W), ptr(rho), ptr(sx), ptr(sxx), C.byref(m)),
               'cna_expr_cross')
         out = (W, rho, sx, sxx, int(m.value))
-        if explicit:
-            return out
-        for a in out[:4]:
-            a.setflags(write=False)
-        self._cross_memo = (key, content, out, {})
+        if not explicit:
+            self._cross_memo = _memo_store(key, content, None, out)
         return out
 
     def cross_extra(self):
         """The dict that goes with the current expr_cross memo (empty after every launch, gone with the memo)."""
-        return {} if self._cross_memo is None else self._cross_memo[3]
+        return {} if self._cross_memo is None else self._cross_memo.extra
 
     CROSS_BY_HOST_BYTES = 1 << 30      # the whole W of expr_cross_by that is taken in one call and kept
 
@@ -1495,26 +1535,21 @@ class Engine(_order.CellOrder):
         expression matrix once per group."""
         if self.nranks != 1 or self.view_local:
             raise NotImplementedError('expr_cross_by needs every row of X on this rank (one rank, replicated view)')
-        import hashlib
         codes = np.ascontiguousarray(codes, dtype=np.int32)
         n_bins = int(n_bins)
         info = self.expression_shape()
         resident = info['format'] != 'none'
-        key = (info['uploads'] if resident else None, self.x_epoch, self.x_generation())
-        digest = (hashlib.blake2b(codes.view(np.uint8).reshape(-1), digest_size=16).hexdigest(), n_bins)
+        key = _x_key(self, info)
+        tag = (array_digest(codes), n_bins)
         sel = None if bins is None else np.asarray(bins, dtype=np.int64).reshape(-1)
         if sel is not None and len(sel) and (sel.min() < 0 or sel.max() >= n_bins):
             raise ValueError('expr_cross_by: bins must lie in [0, n_bins)')
 
         def pick(out):
             return out if sel is None else tuple(a[sel] for a in out)
-        memo = self._cross_by_memo
-        if memo is not None and key[0] is not None and xrow is None and memo[2] == digest:
-            if memo[0] == key:
-                return pick(memo[4])
-            if content is not None and memo[1] == content and memo[0][0] == key[0]:
-                self._cross_by_memo = (key, content) + memo[2:]
-                return pick(memo[4])
+        memo = None if xrow is not None else _memo_lookup(self._cross_by_memo, key, content, tag)
+        if memo is not None:
+            return pick(memo.result)
         g = info['n_genes']
         cols = self.matrix_shape(MAT_X)[1] if resident else 0
         explicit = xrow is not None
@@ -1529,10 +1564,7 @@ class Engine(_order.CellOrder):
             grams = [self.gram_by(xrow, np.where((cd >= b0) & (cd < b0 + gstep), cd - b0, -1), min(gstep, k - b0))[0]
                      for b0 in range(0, k, gstep)]
             Gamma = np.concatenate(grams) if len(grams) > 1 else grams[0]
-            has = np.flatnonzero((xrow >= 0) & (xrow < int(self.x_rows_total)))
-            local = np.full(int(self.x_rows_total), -1, dtype=np.int32)
-            local[xrow[has]] = cd[has]
-            rho = self.matrix_rows_to_bins(MAT_X, local, None, k)[0][0]
+            rho = self.matrix_rows_to_bins(MAT_X, _rows_of_x(xrow, int(self.x_rows_total), cd)[0], None, k)[0][0]
             self.cross_by_launches += 1                               # counted once nothing has been refused
             return W, rho, sx, sxx, m, Gamma
         fits = 8 * n_bins * g * cols <= self.CROSS_BY_HOST_BYTES and 8 * n_bins * cols * cols <= self.CROSS_BY_HOST_BYTES
@@ -1544,16 +1576,13 @@ class Engine(_order.CellOrder):
             self._cross_by_memo = None
             return take(np.where(ok, lut[np.where(ok, codes, -1)], codes).astype(np.int32), len(want))
         out = take(codes, n_bins)
-        if explicit:
-            return pick(out)
-        for a in out:
-            a.setflags(write=False)
-        self._cross_by_memo = (key, content, digest, n_bins, out, {})
+        if not explicit:
+            self._cross_by_memo = _memo_store(key, content, tag, out)
         return pick(out)
 
     def cross_by_extra(self):
         """The dict that goes with the current expr_cross_by memo (empty after every launch, gone with the memo)."""
-        return {} if self._cross_by_memo is None else self._cross_by_memo[5]
+        return {} if self._cross_by_memo is None else self._cross_by_memo.extra
 
     # ---------------------------------------------------------------- synthetic inputs
     def knn_graph(self, X, k):

@@ -15,7 +15,7 @@ import pandas as pd
 
 from ..engine import get_engine
 from ._gene_test import benjamini_hochberg, gene_test
-from ._nam import shard_of
+from ._nam import refuse_sharded
 
 MAX_SET_SIZE = 4096          # members of one set the device takes (csrc/enrich.hip)
 COLUMNS = ['n_given', 'size', 'es', 'nes', 'p', 'q']
@@ -127,9 +127,7 @@ def gene_set_test(data, y, sid_name, gene_sets, batches=None, covs=None, donorid
     if 'return_null' in kwargs:
         raise TypeError("gene_set_test() got multiple values for keyword argument 'return_null'")
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('gene_set_test does not take sharded data or a multi-rank engine yet (the per-gene sums '
-                                  'add over row blocks: one all-reduce away).')
+    refuse_sharded(data, engine, 'gene_set_test', 'the per-gene sums add over row blocks: one all-reduce away')
     genes, null_r = gene_test(data, y, sid_name, batches=batches, covs=covs, donorids=donorids, layer=layer,
                               key_added=key_added, return_null=True, engine=engine, **kwargs)
     res = gene_set_enrich(genes['r'].values, null_r, gene_sets, genes.index, weight=weight, min_size=min_size,

@@ -12,10 +12,10 @@ import numpy as np
 import pandas as pd
 
 from ..engine import get_engine
-from ._genes import check_expression, key_columns
-from ._nam import shard_of
+from ._genes import expression_of, gene_index, key_columns
+from ._nam import refuse_sharded
+from ._strata import levels_of
 
-MAX_LEVELS = 1024
 MAX_ROWS = 4096         # keys x levels, the row cap of cna.ut.expr_to_sample
 
 
@@ -38,35 +38,19 @@ def gene_corr_strata(data, stratification, keys='coef', layer=None, return_withi
 
     At most 1024 levels, and keys x levels <= 4096."""
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('gene_corr_strata does not take sharded data or a multi-rank engine yet (the per-level '
-                                  'sums add over row blocks: one all-reduce away).')
+    refuse_sharded(data, engine, 'gene_corr_strata', 'the per-level sums add over row blocks: one all-reduce away')
     obs = data.obs
     if stratification not in obs:
         raise KeyError(stratification)
     names, V = key_columns(obs, keys)
-    codes, levels = pd.factorize(obs[stratification])           # first appearance; NaN / None -> -1
-    if not 1 <= len(levels) <= MAX_LEVELS:
-        raise ValueError('gene_corr_strata: data.obs[%r] has %d levels, must lie in [1, %d]'
-                         % (stratification, len(levels), MAX_LEVELS))
+    codes, levels = levels_of(obs, stratification, 'gene_corr_strata')
     if len(names) * len(levels) > MAX_ROWS:
         raise ValueError('gene_corr_strata: %d keys x %d levels exceed %d rows; pass fewer keys per call'
                          % (len(names), len(levels), MAX_ROWS))
-    if layer is None:
-        X = getattr(data, 'X', None)
-        if X is None:
-            raise ValueError('data.X is missing: gene_corr_strata needs the expression matrix')
-    else:
-        layers = getattr(data, 'layers', None)
-        if layers is None or layer not in layers:
-            raise KeyError(layer)
-        X = layers[layer]
-    X = check_expression(X, len(obs))
+    X = expression_of(data, layer, 'gene_corr_strata')
     engine.ensure_expression(X)
-    r, within, _ = engine.gene_corr_by(V, np.asarray(codes, dtype=np.int32), len(levels), want_within=bool(return_within))
-    index = getattr(data, 'var_names', None)
-    if index is None or len(index) != X.shape[1]:
-        index = pd.RangeIndex(X.shape[1])
+    r, within, _ = engine.gene_corr_by(V, codes, len(levels), want_within=bool(return_within))
+    index = gene_index(data, X.shape[1])
     level_index = pd.Index(levels, name=stratification)
     r = np.asarray(r, dtype=np.float64)
     if isinstance(keys, str):

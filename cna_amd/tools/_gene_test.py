@@ -14,20 +14,16 @@ linear or quadratic in ``z_p``::
 
 W depends on the dataset, the covariates and the batches, not on the phenotype: one pass over the cells, kept by the
 engine (``Engine.expr_cross``), and the observed r and every null r of every gene are sample-space algebra, genes x
-samples by samples x permutations.  The cells x permutations matrix is never formed.  This module is the host side.
+samples by samples x permutations.  The cells x permutations matrix is never formed.  This module is the host side; the steps
+``cna.tl.gene_test_strata`` takes as well are in tools/_gene_null.py.
 """
-import warnings
-
 import numpy as np
 import pandas as pd
 
 from ..engine import get_engine
-from . import _association as _assoc
-from ._association import association, _draw_null
-from ._genes import check_expression
-from ._nam import shard_of
-
-MAX_NULL = 1000          # the local test's cap on the permutations it uses (_association.py:94)
+from ._gene_null import constant_genes, content_signature, null_phenotypes, warn_smallest_p
+from ._genes import expression_of, gene_index
+from ._nam import refuse_sharded
 
 
 def null_correlations(W, rho, sx, sxx, m, Gamma, Z):
@@ -79,25 +75,6 @@ def permutation_stats(r, null_r):
     return mean, sd, z, p, benjamini_hochberg(p)
 
 
-def _expression(data, layer):
-    if layer is None:
-        X = getattr(data, 'X', None)
-        if X is None:
-            raise ValueError('data.X is missing: gene_test needs the expression matrix')
-    else:
-        layers = getattr(data, 'layers', None)
-        if layers is None or layer not in layers:
-            raise KeyError(layer)
-        X = layers[layer]
-    return check_expression(X, len(data.obs))
-
-
-def _digest(a):
-    import hashlib
-    a = np.ascontiguousarray(a)
-    return hashlib.blake2b(a.view(np.uint8).reshape(-1), digest_size=16).hexdigest()
-
-
 def gene_test(data, y, sid_name, batches=None, covs=None, donorids=None, layer=None, key_added='coef', var_key_added=None,
               return_null=False, engine=None, **kwargs):
     """``association(data, y, sid_name, batches, covs, donorids, key_added=key_added, **kwargs)`` and, for every gene of
@@ -118,74 +95,21 @@ def gene_test(data, y, sid_name, batches=None, covs=None, donorids=None, layer=N
     The one pass over the cells (W = E^T X) depends on the covariates and batches, not on y: the engine keeps it, and a
     further phenotype on the same covariates costs sample-space algebra only."""
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('gene_test does not take sharded data or a multi-rank engine yet (the per-gene sums '
-                                  'add over row blocks: one all-reduce away).')
-    X = _expression(data, layer)
-    for name in ('return_full', 'engine'):
-        if name in kwargs:
-            raise TypeError("gene_test() got an unexpected keyword argument '%s'" % name)
-    seed = kwargs.get('seed')
-    Nnull = kwargs.get('Nnull', 1000)
-    state0 = np.random.get_state() if seed is None else None
-    _assoc._tolerate.no_fdr = True
-    try:
-        res = association(data, y, sid_name, batches=batches, covs=covs, donorids=donorids, key_added=key_added,
-                          return_full=True, engine=engine, **kwargs)
-    finally:
-        _assoc._tolerate.no_fdr = False
-
-    # the null phenotypes this association used: the same draw again, numpy's generator put back afterwards
-    index = res.M.index
-    yv = np.asarray(y.reindex(index).values, dtype=np.float64)
-    bv = np.ones(len(index)) if batches is None else batches.reindex(index).values
-    dv = None if donorids is None else donorids.reindex(index).values
-    state1 = np.random.get_state()
-    try:
-        if state0 is not None:
-            np.random.set_state(state0)
-        y_std, y_null = _draw_null(yv, bv, dv, Nnull=Nnull, force_permute_all=kwargs.get('force_permute_all', False), seed=seed)
-    finally:
-        np.random.set_state(state1)
-    P = min(MAX_NULL, int(Nnull))
-    Mv = np.asarray(res.M, dtype=np.float64)
-    Z = Mv @ np.asarray(y_null, dtype=np.float64)[:, :P]
-    Z = Z / Z.std(axis=0, ddof=1)                              # _association.py:96-97 (pandas' std: ddof=1)
-    # the observed phenotype: standardised, not residualised (_association.py:77) -- so that r is gene_corr's
-    Zall = np.column_stack([np.asarray(y_std, dtype=np.float64), Z])
+    refuse_sharded(data, engine, 'gene_test', 'the per-gene sums add over row blocks: one all-reduce away')
+    X = expression_of(data, layer, 'gene_test')
+    res, Zall, P = null_phenotypes(data, y, sid_name, batches, covs, donorids, key_added, engine, kwargs, 'gene_test')
 
     engine.ensure_expression(X)
     Gamma = engine.gram_held()
-    kept = np.asarray(res.kept, dtype=bool)
-    # What this X was made from, for the engine's memo of W: every association rebuilds X, so the engine's own key moves
-    # with every call; an equal signature of the NAM, the kept cells, the samples, the projector (covariates, batches,
-    # ridge) and the Gram matrix' bits says the rebuilt X is the same one.  No signature of the NAM: no carry-over.
-    content = None
-    if getattr(engine, '_nam_sig', None) is not None:
-        content = (repr(engine._nam_sig), len(kept), None if kept.all() else _digest(kept), tuple(map(str, index)),
-                   _digest(Mv), _digest(Gamma))
-    W, rho, sx, sxx, m = engine.expr_cross(content=content)
+    W, rho, sx, sxx, m = engine.expr_cross(content=content_signature(engine, res, Gamma))
     r_all = null_correlations(W, rho, sx, sxx, m, Gamma, Zall)
-    # constant genes, decided as gene_corr decides them (exactly: minimum == maximum over the kept cells) -- by gene_corr
-    # itself, against a column that is finite on the kept cells and varies there.  They depend on E and the kept cells
-    # only, so the mask is kept beside W and a further phenotype does not pass over the matrix for it either
-    extra = engine.cross_extra()
-    constant = extra.get('constant')
-    if constant is None:
-        probe = np.where(kept, np.arange(len(kept), dtype=np.float64), np.nan)
-        constant = np.isnan(engine.gene_corr(probe[None, :])[0])
-        extra['constant'] = constant
+    constant = constant_genes(np.asarray(res.kept, dtype=bool), engine.cross_extra(), lambda V: engine.gene_corr(V)[0])
     r_all[constant] = np.nan
     r, null_r = np.ascontiguousarray(r_all[:, 0]), np.ascontiguousarray(r_all[:, 1:])
     mean, sd, z, p, q = permutation_stats(r, null_r)
 
-    G = X.shape[1]
-    if 1.0 / (P + 1) > 0.05 / G:
-        warnings.warn(('the smallest p-value {} permutations can give, {:.3g}, is above 0.05 / {} genes. ' +
-                       'Consider increasing Nnull').format(P, 1.0 / (P + 1), G))
-    gindex = getattr(data, 'var_names', None)
-    if gindex is None or len(gindex) != G:
-        gindex = pd.RangeIndex(G)
+    warn_smallest_p(P, X.shape[1])
+    gindex = gene_index(data, X.shape[1])
     out = pd.DataFrame({'r': r, 'null_mean': mean, 'null_sd': sd, 'z': z, 'p': p, 'q': q}, index=gindex,
                        columns=['r', 'null_mean', 'null_sd', 'z', 'p', 'q'])
     out.attrs['p'] = res.p                                     # the association's global p-value, as a plain call returns it

@@ -12,80 +12,22 @@ linear or quadratic in ``z_p`` there too (tools/_gene_test.py), over the level's
     sum_{i in C_l} c_p[i]      = (rho_l . z_p) / N          rho_l   = column sums of X_{C_l}  (cna_matrix_to_bins)
     sum_{i in C_l} c_p[i]^2    = z_p^T Gamma_l z_p / N^2    Gamma_l = X_{C_l}^T X_{C_l}    (cna_gram_by)
 
-so ``null_correlations`` runs once per level, unchanged.  None of the sums depends on y: the engine keeps them
+so ``gene_test``'s own steps serve here (tools/_gene_null.py: ``null_phenotypes``, ``content_signature``,
+``constant_genes``) and ``null_correlations`` runs once per level, unchanged.  None of the sums depends on y: the engine keeps them
 (``Engine.expr_cross_by``) and a further phenotype on the same covariates and clustering costs sample-space algebra only.
 This module is the host side.
 """
-import warnings
-
 import numpy as np
 import pandas as pd
 
 from ..engine import get_engine
-from . import _association as _assoc
-from ._association import association, _draw_null
-from ._gene_test import MAX_NULL, _digest, _expression, null_correlations, permutation_stats
-from ._nam import shard_of
+from ._gene_null import constant_genes, content_signature, null_phenotypes, warn_smallest_p
+from ._gene_test import null_correlations, permutation_stats
+from ._genes import expression_of, gene_index
+from ._nam import refuse_sharded
+from ._strata import levels_of
 
-MAX_LEVELS = 1024
 STATISTICS = ['r', 'null_mean', 'null_sd', 'z', 'p', 'q']
-
-
-# ------------------------------------------------------------------ gene_test's pieces, as functions
-def null_phenotypes(data, y, sid_name, batches, covs, donorids, key_added, engine, kwargs, who):
-    """gene_test's steps up to the cells as one function (tools/_gene_test.py holds them inline, unchanged): the
-    association (its FDR column optional: ``_tolerate.no_fdr``), then the null phenotypes it used -- the same draw again, numpy's generator put back afterwards.
-    -> (res, Zall, P): the full result, samples x (1 + P) with the standardised observed phenotype first and the P =
-    min(1000, Nnull) conditioned, standardised null phenotypes behind it."""
-    for name in ('return_full', 'engine'):
-        if name in kwargs:
-            raise TypeError("%s() got an unexpected keyword argument '%s'" % (who, name))
-    seed = kwargs.get('seed')
-    Nnull = kwargs.get('Nnull', 1000)
-    state0 = np.random.get_state() if seed is None else None
-    _assoc._tolerate.no_fdr = True
-    try:
-        res = association(data, y, sid_name, batches=batches, covs=covs, donorids=donorids, key_added=key_added,
-                          return_full=True, engine=engine, **kwargs)
-    finally:
-        _assoc._tolerate.no_fdr = False
-
-    # the null phenotypes this association used: the same draw again, numpy's generator put back afterwards
-    index = res.M.index
-    yv = np.asarray(y.reindex(index).values, dtype=np.float64)
-    bv = np.ones(len(index)) if batches is None else batches.reindex(index).values
-    dv = None if donorids is None else donorids.reindex(index).values
-    state1 = np.random.get_state()
-    try:
-        if state0 is not None:
-            np.random.set_state(state0)
-        y_std, y_null = _draw_null(yv, bv, dv, Nnull=Nnull, force_permute_all=kwargs.get('force_permute_all', False), seed=seed)
-    finally:
-        np.random.set_state(state1)
-    P = min(MAX_NULL, int(Nnull))
-    Mv = np.asarray(res.M, dtype=np.float64)
-    Z = Mv @ np.asarray(y_null, dtype=np.float64)[:, :P]
-    Z = Z / Z.std(axis=0, ddof=1)                              # _association.py:96-97 (pandas' std: ddof=1)
-    # the observed phenotype: standardised, not residualised (_association.py:77) -- so that r is gene_corr's
-    return res, np.column_stack([np.asarray(y_std, dtype=np.float64), Z]), P
-
-
-def content_signature(engine, res, Gamma):
-    """What this X was made from, for the engine's memos of the cell-sized sums: every association rebuilds X, so the
-    engine's own key moves with every call; an equal signature of the NAM, the kept cells, the samples, the projector
-    (covariates, batches, ridge) and the Gram matrix' bits says the rebuilt X is the same one.  No signature of the NAM:
-    None, no carry-over."""
-    if getattr(engine, '_nam_sig', None) is None:
-        return None
-    kept = np.asarray(res.kept, dtype=bool)
-    return (repr(engine._nam_sig), len(kept), None if kept.all() else _digest(kept), tuple(map(str, res.M.index)),
-            _digest(np.asarray(res.M, dtype=np.float64)), _digest(Gamma))
-
-
-def warn_smallest_p(P, G):
-    if 1.0 / (P + 1) > 0.05 / G:
-        warnings.warn(('the smallest p-value {} permutations can give, {:.3g}, is above 0.05 / {} genes. ' +
-                       'Consider increasing Nnull').format(P, 1.0 / (P + 1), G))
 
 
 def level_statistics(sums, Zall, constant):
@@ -126,7 +68,7 @@ def gene_test_strata(data, y, sid_name, stratification, batches=None, covs=None,
     P' = min(1000, Nnull) permuted phenotypes the association drew (same ``seed`` / same state of numpy's global
     generator, which is left where the association left it).
 
-    Levels in order of first appearance (``pd.factorize``); cells whose level is NaN / None are left out; at most 1024
+    Levels in order of first appearance; cells whose level is NaN / None are left out; at most 1024
     levels.  Returns a float64 DataFrame indexed like ``gene_corr``'s with a column MultiIndex ``(level, statistic)``,
     level-major, the statistics ``r, null_mean, null_sd, z, p, q`` as in ``gene_test``; ``q`` is Benjamini-Hochberg inside
     each level over the genes with a finite p.  ``frame.attrs``: ``p`` the association's global p-value, ``n_null`` = P',
@@ -138,42 +80,22 @@ def gene_test_strata(data, y, sid_name, stratification, batches=None, covs=None,
     their results, and a further phenotype costs sample-space algebra only.  When the per-level sums of all levels do
     not fit 1 GiB they are taken in groups of levels and not kept (``Engine.expr_cross_by``)."""
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('gene_test_strata does not take sharded data or a multi-rank engine yet (the per-level '
-                                  'sums add over row blocks: one all-reduce away).')
-    obs = data.obs
-    if stratification not in obs:
-        raise KeyError(stratification)
-    codes, levels = pd.factorize(obs[stratification])           # first appearance; NaN / None -> -1
-    if not 1 <= len(levels) <= MAX_LEVELS:
-        raise ValueError('gene_test_strata: data.obs[%r] has %d levels, must lie in [1, %d]'
-                         % (stratification, len(levels), MAX_LEVELS))
-    codes = np.ascontiguousarray(codes, dtype=np.int32)
+    refuse_sharded(data, engine, 'gene_test_strata', 'the per-level sums add over row blocks: one all-reduce away')
+    codes, levels = levels_of(data.obs, stratification, 'gene_test_strata')
     L = len(levels)
-    X = _expression(data, layer)
+    X = expression_of(data, layer, 'gene_test_strata')
     res, Zall, P = null_phenotypes(data, y, sid_name, batches, covs, donorids, key_added, engine, kwargs, 'gene_test_strata')
 
     engine.ensure_expression(X)
     content = content_signature(engine, res, engine.gram_held())
     sums = engine.expr_cross_by(codes, L, content=content)
-    # constant genes, decided as gene_corr_strata decides them (exactly: minimum == maximum over the level's kept cells) --
-    # by gene_corr_by itself, against a column that is finite on the kept cells and varies there.  They depend on E, the
-    # kept cells and the clustering only, so the mask is kept beside the sums
-    extra = engine.cross_by_extra()
-    constant = extra.get('constant')
-    if constant is None:
-        kept = np.asarray(res.kept, dtype=bool)
-        probe = np.where(kept, np.arange(len(kept), dtype=np.float64), np.nan)
-        constant = np.isnan(engine.gene_corr_by(probe[None, :], codes, L, want_within=False)[0][0])
-        extra['constant'] = constant
+    # per level (gene_corr_by, as gene_corr_strata decides them): the mask depends on the clustering too, as the sums do
+    constant = constant_genes(np.asarray(res.kept, dtype=bool), engine.cross_by_extra(),
+                              lambda V: engine.gene_corr_by(V, codes, L, want_within=False)[0][0])
     table, null_r = level_statistics(sums, Zall, constant)
 
-    G = X.shape[1]
-    warn_smallest_p(P, G)
-    gindex = getattr(data, 'var_names', None)
-    if gindex is None or len(gindex) != G:
-        gindex = pd.RangeIndex(G)
-    out = strata_frame(table, levels, stratification, gindex)
+    warn_smallest_p(P, X.shape[1])
+    out = strata_frame(table, levels, stratification, gene_index(data, X.shape[1]))
     out.attrs['p'] = res.p                                     # the association's global p-value, as a plain call returns it
     out.attrs['n_null'] = P
     out.attrs['n_cells'] = pd.Series(np.asarray(sums[4], dtype=np.int64), index=pd.Index(levels, name=stratification))

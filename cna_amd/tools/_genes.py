@@ -14,7 +14,7 @@ import pandas as pd
 import scipy.sparse as sp
 
 from ..engine import get_engine
-from ._nam import shard_of
+from ._nam import refuse_sharded
 
 MAX_KEYS = 16
 
@@ -45,6 +45,34 @@ def check_expression(X, n_obs):
     return X
 
 
+def expression_of(data, layer, who):
+    """``data.X``, or ``data.layers[layer]``, checked (check_expression); ValueError / KeyError when it is not there."""
+    if layer is None:
+        X = getattr(data, 'X', None)
+        if X is None:
+            raise ValueError('data.X is missing: %s needs the expression matrix' % who)
+    else:
+        layers = getattr(data, 'layers', None)
+        if layers is None or layer not in layers:
+            raise KeyError(layer)
+        X = layers[layer]
+    return check_expression(X, len(data.obs))
+
+
+def gene_index(data, n_genes):
+    """``data.var_names`` when there are n_genes of them, else a RangeIndex."""
+    index = getattr(data, 'var_names', None)
+    return pd.RangeIndex(n_genes) if index is None or len(index) != n_genes else index
+
+
+def numeric_column(obs, k):
+    """data.obs[k] as contiguous float64, or TypeError."""
+    try:
+        return np.ascontiguousarray(np.asarray(obs[k].values, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise TypeError('data.obs[%r] is not numeric' % (k,)) from None
+
+
 def key_columns(obs, keys):
     """(names, q x cells float64) of the requested columns of data.obs."""
     names = [keys] if isinstance(keys, str) else list(keys)
@@ -56,10 +84,7 @@ def key_columns(obs, keys):
     for k in names:
         if k not in obs:
             raise KeyError(k)
-        try:
-            cols.append(np.asarray(obs[k].values, dtype=np.float64))
-        except (TypeError, ValueError):
-            raise TypeError('data.obs[%r] is not numeric' % (k,)) from None
+        cols.append(numeric_column(obs, k))
     return names, np.ascontiguousarray(np.stack(cols))
 
 
@@ -78,25 +103,12 @@ def gene_corr(data, keys='coef', layer=None, key_added=None, engine=None):
     Returns a DataFrame (index ``data.var_names`` when there are any), one float64 column per key; ``key_added``
     (a prefix) also writes ``data.var[key_added + key]``."""
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('gene_corr does not take sharded data or a multi-rank engine yet (the per-gene sums '
-                                  'add over row blocks: one all-reduce away).')
+    refuse_sharded(data, engine, 'gene_corr', 'the per-gene sums add over row blocks: one all-reduce away')
     names, V = key_columns(data.obs, keys)
-    if layer is None:
-        X = getattr(data, 'X', None)
-        if X is None:
-            raise ValueError('data.X is missing: gene_corr needs the expression matrix')
-    else:
-        layers = getattr(data, 'layers', None)
-        if layers is None or layer not in layers:
-            raise KeyError(layer)
-        X = layers[layer]
-    X = check_expression(X, len(data.obs))
+    X = expression_of(data, layer, 'gene_corr')
     engine.ensure_expression(X)
     r = engine.gene_corr(V)
-    index = getattr(data, 'var_names', None)
-    if index is None or len(index) != X.shape[1]:
-        index = pd.RangeIndex(X.shape[1])
+    index = gene_index(data, X.shape[1])
     out = pd.DataFrame({k: r[j] for j, k in enumerate(names)}, index=index, columns=names)
     if key_added is not None:
         if getattr(data, 'var', None) is None:

@@ -261,15 +261,20 @@ def _as_csr(a):
     return sp.csr_matrix(a)
 
 
+def first_appearance(col):
+    """(codes, Index of the distinct values) of a column of data.obs, in order of first appearance; NaN / None -> code -1."""
+    codes, uniques = pd.factorize(col)
+    return codes, pd.Index(uniques)
+
+
 def sample_codes(col):
     """Column order of ``pd.get_dummies(obs[sid])`` (_nam.py:51): category order for a
     categorical column (unused categories included), sorted unique labels otherwise."""
     if isinstance(col.dtype, pd.CategoricalDtype):
         return np.asarray(col.cat.codes, dtype=np.int32), pd.Index(col.cat.categories)
-    # factorize in order of appearance, then rank the (few) labels: pandas' sort=True re-maps the
+    # in order of appearance, then rank the (few) labels: pandas' sort=True re-maps the
     # per-cell codes through a generic take that is several times slower than the hashing itself
-    codes, uniques = pd.factorize(col)
-    uniques = pd.Index(uniques)
+    codes, uniques = first_appearance(col)
     order = uniques.argsort()
     rank = np.empty(len(order) + 1, dtype=np.int32)
     rank[order] = np.arange(len(order), dtype=np.int32)
@@ -278,15 +283,6 @@ def sample_codes(col):
 
 
 _codes_cache = {}
-
-
-try:
-    from xxhash import xxh3_128_intdigest as _content_hash
-except Exception:   # pragma: no cover - xxhash not installed
-    import hashlib
-
-    def _content_hash(buf):
-        return int.from_bytes(hashlib.blake2b(buf, digest_size=16).digest(), 'little')
 
 
 def _content_hash_threaded(arr):
@@ -401,6 +397,12 @@ def shard_of(data):
     info = getattr(data, 'uns', None)
     info = info.get('cna_shard') if hasattr(info, 'get') else None
     return None if info is None else (int(info['row0']), int(info['n_global']))
+
+
+def refuse_sharded(data, engine, who, remedy):
+    """NotImplementedError for a tool that needs every cell on one rank; `remedy`: what its sums would take across ranks."""
+    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
+        raise NotImplementedError('%s does not take sharded data or a multi-rank engine yet (%s).' % (who, remedy))
 
 
 _global_codes_cache = {}

@@ -18,8 +18,9 @@ import pandas as pd
 
 from .._ffi import MAT_NAM
 from ..engine import get_engine
-from ._nam import _nam_device, sample_codes_cached, shard_of
-from ._strata import FDR_THRESH, MAX_LEVELS, _numeric
+from ._genes import numeric_column
+from ._nam import _nam_device, refuse_sharded, sample_codes_cached
+from ._strata import FDR_THRESH, levels_of
 
 MAX_WEIGHTS = 16
 MAX_SUMS = 4096         # weight columns x levels of one device pass
@@ -46,9 +47,7 @@ def nam_strata(data, stratification, sid_name, weights=None, sign_of=None, fdr_t
     ``return_counts=True`` returns ``(result, counts)``: a frame levels x (one column per result frame) of the contributing
     cells, int64."""
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('nam_strata does not take sharded data or a multi-rank engine yet (the per-level sums '
-                                  'add over row blocks: an all-reduce away).')
+    refuse_sharded(data, engine, 'nam_strata', 'the per-level sums add over row blocks: an all-reduce away')
     obs = data.obs
     for k in (stratification, sid_name):
         if k not in obs:
@@ -67,11 +66,11 @@ def nam_strata(data, stratification, sid_name, weights=None, sign_of=None, fdr_t
         has_fdr = fkey in obs
         if not has_fdr and fdr_thresh is not None:
             raise KeyError(fkey)
-        v = _numeric(obs, sign_of)
+        v = numeric_column(obs, sign_of)
         with np.errstate(invalid='ignore'):
             passes = np.isfinite(v)
             if has_fdr:
-                passes &= _numeric(obs, fkey) <= (FDR_THRESH if fdr_thresh is None else float(fdr_thresh))
+                passes &= numeric_column(obs, fkey) <= (FDR_THRESH if fdr_thresh is None else float(fdr_thresh))
             W = np.stack([passes & (v > 0), passes & (v < 0)]).astype(np.float64)
         names, single = ['pos', 'neg'], False
     elif weights is not None:
@@ -81,19 +80,15 @@ def nam_strata(data, stratification, sid_name, weights=None, sign_of=None, fdr_t
         for k in names:
             if k not in obs:
                 raise KeyError(k)
-        W = np.stack([_numeric(obs, k) for k in names])
+        W = np.stack([numeric_column(obs, k) for k in names])
     if keep is not None:
         keep = np.asarray(keep)
         if keep.dtype != bool or keep.shape != (n,):
             raise ValueError('nam_strata: keep must be one bool per cell')
-    codes, levels = pd.factorize(obs[stratification])           # first appearance; NaN / None -> -1
-    if not 1 <= len(levels) <= MAX_LEVELS:
-        raise ValueError('nam_strata: data.obs[%r] has %d levels, must lie in [1, %d]'
-                         % (stratification, len(levels), MAX_LEVELS))
+    codes, levels = levels_of(obs, stratification, 'nam_strata')
     q = 1 if W is None else len(W)
     if q * len(levels) > MAX_SUMS:
         raise ValueError('nam_strata: %d weight columns x %d levels, at most %d sums in one pass' % (q, len(levels), MAX_SUMS))
-    codes = np.asarray(codes, dtype=np.int32)
     if keep is not None:
         codes = np.where(keep, codes, np.int32(-1)).astype(np.int32)
     labels, _ = _nam_device(engine, data, sid_name, nsteps=nsteps, self_weight=self_weight,

@@ -19,18 +19,24 @@ import numpy as np
 import pandas as pd
 
 from ..engine import get_engine
-from ._nam import shard_of
+from ._genes import numeric_column
+from ._nam import first_appearance, refuse_sharded
 
 MAX_LEVELS = 1024
 MAX_POINTS = 1024
 FDR_THRESH = 0.1        # plotting/_umap.py:10, umap_ncorr's default
 
 
-def _numeric(obs, k):
-    try:
-        return np.ascontiguousarray(np.asarray(obs[k].values, dtype=np.float64))
-    except (TypeError, ValueError):
-        raise TypeError('data.obs[%r] is not numeric' % (k,)) from None
+def levels_of(obs, stratification, who, max_levels=MAX_LEVELS):
+    """(int32 code per cell, the levels) of ``data.obs[stratification]``: levels in order of first appearance, NaN / None
+    -> code -1.  KeyError without the column; ValueError, under `who`'s name, unless there are 1 to max_levels levels."""
+    if stratification not in obs:
+        raise KeyError(stratification)
+    codes, levels = first_appearance(obs[stratification])
+    if not 1 <= len(levels) <= max_levels:
+        raise ValueError('%s: data.obs[%r] has %d levels, must lie in [1, %d]'
+                         % (who, stratification, len(levels), max_levels))
+    return np.ascontiguousarray(codes, dtype=np.int32), levels
 
 
 def _bandwidth(bw_method):
@@ -72,9 +78,8 @@ def coef_strata(data, stratification, key='coef', fdr_thresh=None, points=100, b
 
     At most 1024 levels and 1024 points."""
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('coef_strata does not take sharded data or a multi-rank engine yet (the per-level sums '
-                                  'add over row blocks, the median and the density need every block: a gather away).')
+    refuse_sharded(data, engine, 'coef_strata', 'the per-level sums add over row blocks, the median and the density need '
+                                                'every block: a gather away')
     obs = data.obs
     for k in (stratification, key):
         if k not in obs:
@@ -83,18 +88,15 @@ def coef_strata(data, stratification, key='coef', fdr_thresh=None, points=100, b
     has_fdr = fkey in obs
     if not has_fdr and fdr_thresh is not None:
         raise KeyError(fkey)
-    v = _numeric(obs, key)
-    fdr = _numeric(obs, fkey) if has_fdr else None
+    v = numeric_column(obs, key)
+    fdr = numeric_column(obs, fkey) if has_fdr else None
     thresh = FDR_THRESH if fdr_thresh is None else float(fdr_thresh)
     if isinstance(points, bool) or int(points) != points or not 1 <= int(points) <= MAX_POINTS:
         raise ValueError('points must be an integer in [1, %d], got %r' % (MAX_POINTS, points))
     points = int(points)
     bw_kind, bw_value = _bandwidth(bw_method)
-    codes, levels = pd.factorize(obs[stratification])           # first appearance; NaN / None -> -1
-    if not 1 <= len(levels) <= MAX_LEVELS:
-        raise ValueError('coef_strata: data.obs[%r] has %d levels, must lie in [1, %d]'
-                         % (stratification, len(levels), MAX_LEVELS))
-    r = engine.coef_strata(v, fdr, np.asarray(codes, dtype=np.int32), len(levels), thresh, points, bw_kind, bw_value)
+    codes, levels = levels_of(obs, stratification, 'coef_strata')
+    r = engine.coef_strata(v, fdr, codes, len(levels), thresh, points, bw_kind, bw_value)
     kept = np.asarray(r['n_kept'], dtype=np.int64)
     with np.errstate(invalid='ignore', divide='ignore'):
         sd = np.where(kept >= 2, np.sqrt(np.asarray(r['ssd']) / (kept - 1.0)), np.nan)

@@ -10,17 +10,11 @@ import numpy as np
 import pandas as pd
 
 from ..engine import get_engine
-from ..tools._genes import check_expression
-from ..tools._nam import shard_of
+from ..tools._genes import expression_of, gene_index
+from ..tools._nam import first_appearance, refuse_sharded
 
 MAX_ROWS = 4096
 AGGREGATES = ('mean', 'sum', 'frac')
-
-
-def _first_appearance(col):
-    """(int64 codes, Index of the distinct values) in order of first appearance; NaN / None -> code -1."""
-    codes, uniques = pd.factorize(col)
-    return np.asarray(codes, dtype=np.int64), pd.Index(uniques)
 
 
 def expr_to_sample(data, sid_name, layer=None, aggregate='mean', groupby=None, return_counts=False, engine=None):
@@ -40,19 +34,17 @@ def expr_to_sample(data, sid_name, layer=None, aggregate='mean', groupby=None, r
     if aggregate not in AGGREGATES:
         raise ValueError("aggregate must be one of 'mean', 'sum', 'frac', got %r" % (aggregate,))
     engine = engine or get_engine()
-    if shard_of(data) is not None or int(getattr(engine, 'nranks', 1)) > 1:
-        raise NotImplementedError('expr_to_sample does not take sharded data or a multi-rank engine yet (the per-row sums '
-                                  'add over row blocks: one all-reduce away).')
+    refuse_sharded(data, engine, 'expr_to_sample', 'the per-row sums add over row blocks: one all-reduce away')
     obs = data.obs
     for k in (sid_name, groupby):
         if k is not None and k not in obs:
             raise KeyError(k)
-    scode, samples = _first_appearance(obs[sid_name])
+    scode, samples = first_appearance(obs[sid_name])
     if groupby is None:
         codes, n_levels = scode, 1
         index = samples
     else:
-        lcode, levels = _first_appearance(obs[groupby])
+        lcode, levels = first_appearance(obs[groupby])
         n_levels = len(levels)
         codes = np.where((scode < 0) | (lcode < 0), -1, scode * n_levels + lcode)
         index = pd.MultiIndex.from_product([samples, levels], names=[sid_name, groupby])
@@ -60,25 +52,13 @@ def expr_to_sample(data, sid_name, layer=None, aggregate='mean', groupby=None, r
     if not 1 <= n_rows <= MAX_ROWS:
         raise ValueError('expr_to_sample: %d samples x %d levels = %d rows, must lie in [1, %d]'
                          % (len(samples), n_levels, n_rows, MAX_ROWS))
-    if layer is None:
-        X = getattr(data, 'X', None)
-        if X is None:
-            raise ValueError('data.X is missing: expr_to_sample needs the expression matrix')
-    else:
-        layers = getattr(data, 'layers', None)
-        if layers is None or layer not in layers:
-            raise KeyError(layer)
-        X = layers[layer]
-    X = check_expression(X, len(obs))
+    X = expression_of(data, layer, 'expr_to_sample')
     engine.ensure_expression(X)
     sums, counts = engine.expr_to_bins(codes.astype(np.int32), n_rows, 1 if aggregate == 'frac' else 0)
     if aggregate != 'sum':
         with np.errstate(invalid='ignore', divide='ignore'):
             sums = sums / np.asarray(counts, dtype=np.float64)[:, None]
-    columns = getattr(data, 'var_names', None)
-    if columns is None or len(columns) != X.shape[1]:
-        columns = pd.RangeIndex(X.shape[1])
-    frame = pd.DataFrame(sums, index=index, columns=columns)
+    frame = pd.DataFrame(sums, index=index, columns=gene_index(data, X.shape[1]))
     if return_counts:
         return frame, pd.Series(np.asarray(counts, dtype=np.int64), index=index)
     return frame

@@ -319,10 +319,10 @@ def test_whole_call_against_the_materialised_oracle(whole):
 
 
 def test_one_level_of_all_cells_is_gene_test(whole):
-    """gene_test_strata restates gene_test's steps up to the cells (the association under _tolerate.no_fdr, the re-draw of the
-    null phenotypes, Zall) as functions of its own module, because tools/_gene_test.py holds them inline.  This keeps the
-    two from drifting apart: with every cell in one level the two tools must return the same r, the same null, the same p
-    and q, write the same columns and leave numpy's generator in the same place -- with a seed and without."""
+    """gene_test_strata takes gene_test's steps up to the cells (the association under _tolerate.no_fdr, the re-draw of the
+    null phenotypes, Zall) from tools/_gene_null.py, as gene_test does; what differs is the engine's sums.  With every cell in one level the
+    two tools must return the same r, the same null, the same p and q, write the same columns and leave numpy's generator
+    in the same place -- with a seed and without."""
     import cna_amd as cna
     data, y, batches, covs, E, call = strata_case()
     for seed in (3, None):
