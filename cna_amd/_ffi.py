@@ -153,6 +153,8 @@ SIGNATURES = {
     'cna_expr_cross_by': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     'cna_gram_by': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    'cna_coef_raster': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double,
+                                  C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8),
 }
 
 MAT_NAM, MAT_X, MAT_PROJ = 0, 1, 2
@@ -183,7 +185,8 @@ class AssocOut(C.Structure):
 KERNELS = ['colsum', 'nam_first', 'nam_step', 'batch_kurtosis', 'zero_variance', 'select', 'resid_xb',
            'standardize', 'gram', 'gram_reduce', 'ncorrs', 'null_local', 'obs_counts', 'percell_fdr',
            'project_xb', 'transpose', 'rccl', 'condition', 'global_test', 'nam_step_sparse', 'halo_exchange', 'halo_wait',
-           'matrix_bins_sort', 'matrix_bins_sum', 'enrich_positions', 'enrich_extremes', 'expr_cross_by', 'gram_by']
+           'matrix_bins_sort', 'matrix_bins_sum', 'enrich_positions', 'enrich_extremes', 'expr_cross_by', 'gram_by',
+           'raster_upload', 'raster', 'raster_fetch']
 
 _lib = None
 

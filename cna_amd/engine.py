@@ -1352,6 +1352,39 @@ class Engine(_order.CellOrder):
                                                                'max', 'vals')]), 'cna_coef_strata')
         return out
 
+    def coef_raster(self, xy, V, FDR, has_fdr, fdr_thresh, extent, width, height, radius=0):
+        """Per-pixel counts, sums and extremes of per-cell columns on a 2-D embedding (cna_coef_raster): `xy` cells x 2
+        float64, `V` q x cells float64 (NaN / inf = the cell does not pass), `FDR` the same shape or None, `has_fdr` one
+        flag per key (a key without one passes every finite value), `extent` (x0, x1, y0, y1) or None = the finite cells'
+        min and max, found on the device.  Returns a dict: extent (4-tuple), n int64[H, W], n_outside int, n_pass
+        int64[q, H, W], sum, top, bottom float64[q, H, W], covered bool[H, W], absmax float64[q]; with radius > 0 top,
+        bottom and covered are dilated by the disc.  ValueError when no cell has finite coordinates.  Needs no graph and no
+        resident expression matrix; `drop_expression` frees its device buffers."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        V = _f64(V)
+        has_fdr = np.ascontiguousarray(has_fdr, dtype=np.int32)
+        if FDR is not None:
+            FDR = _f64(FDR)
+        if xy.ndim != 2 or xy.shape[1] != 2 or V.ndim != 2 or V.shape[1] != xy.shape[0] or has_fdr.shape != (V.shape[0],) \
+                or (FDR is not None and FDR.shape != V.shape) or (FDR is None and has_fdr.any()):
+            raise ValueError('coef_raster: xy is cells x 2, V and FDR are keys x cells, has_fdr has one flag per key')
+        q, W, H = int(V.shape[0]), int(width), int(height)
+        # sizes the library refuses get one-pixel outputs: it writes nothing then
+        Wp, Hp = (W, H) if 1 <= W <= 4096 and 1 <= H <= 4096 and q * W * H <= 2 ** 22 else (1, 1)
+        ext = np.zeros(4) if extent is None else np.array(extent, dtype=np.float64).reshape(4)
+        out = {'n': np.empty((Hp, Wp), dtype=np.int64), 'n_pass': np.empty((q, Hp, Wp), dtype=np.int64)}
+        out.update({k: np.empty((q, Hp, Wp)) for k in ('sum', 'top', 'bottom')})
+        covered = np.empty((Hp, Wp), dtype=np.uint8)
+        absmax, n_outside = np.empty(q), np.zeros(1, dtype=np.int64)
+        check(self.lib.cna_coef_raster(self.h, ptr(xy), ptr(V), ptr(FDR), ptr(has_fdr), q, xy.shape[0], float(fdr_thresh),
+                                       ptr(ext), int(extent is None), W, H, int(radius), ptr(out['n']), ptr(n_outside),
+                                       ptr(out['n_pass']), ptr(out['sum']), ptr(out['top']), ptr(out['bottom']), ptr(covered),
+                                       ptr(absmax)), 'cna_coef_raster')
+        if np.isnan(ext).any():
+            raise ValueError('coef_raster: no cell has finite coordinates, so there is no extent')
+        out.update(extent=tuple(float(e) for e in ext), n_outside=int(n_outside[0]), covered=covered.view(np.bool_), absmax=absmax)
+        return out
+
     def matrix_to_bins(self, which, codes, W=None, n_bins=None):
         """Weighted per-bin sums over the rows of the resident NAM (MAT_NAM) or of the working matrix X (MAT_X), on the
         device (cna_matrix_to_bins): `codes` int32 per cell in the CALLER's order, -1 = cell left out; `W` q x cells

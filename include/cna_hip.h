@@ -65,6 +65,10 @@ enum {
    * and their folds; the checks of xrow and the sort's count before them are outside (csrc/expr_cross_by.hip,
    * csrc/gram_by.hip) */
   CNA_K_EXPR_CROSS_BY, CNA_K_GRAM_BY,
+  /* cna_coef_raster on the expression stream: the copies of its columns to the device; everything from the extent to the
+   * dilated images, its waits for the extent and for the chunk counts included; the copies of the images back
+   * (csrc/raster.hip) */
+  CNA_K_RASTER_UPLOAD, CNA_K_RASTER, CNA_K_RASTER_FETCH,
   CNA_K_COUNT
 };
 
@@ -613,7 +617,7 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
- * cna_enrichment_extremes, cna_expr_cross_by and cna_gram_by:
+ * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by and cna_coef_raster:
  * cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
@@ -830,6 +834,51 @@ int  cna_matrix_to_bins(cna_ctx* ctx, int which, const int32_t* codes, const dou
 int  cna_enrichment_extremes(cna_ctx* ctx, const double* R, int64_t n_cols, int64_t n_genes, const int64_t* set_ptr,
                              const int32_t* set_genes, int n_sets, int weight, double* up_out, double* down_out,
                              int32_t* size_out, int32_t* valid_out);
+
+/* ---- the coefficient on the embedding, as images (csrc/raster.hip) ---------------------------- */
+/* The picture the reference's workflow draws right after cna.tl.association, as numbers:
+ *     cna.pl.umap_ncorr(d, key='case_coef')                  (demo/demo.ipynb 1.2 and 1.3; plotting/_umap.py:6-36)
+ * draws every cell in grey and on top the cells with coef_fdr <= 0.1 coloured by coefficient, scanpy sorting the points so
+ * that the highest lies on top; demo 3.2.1 draws sc.pl.umap(d, color='NAMPC1', cmap='seismic') the same way without an
+ * fdr.  Here the cells are reduced to the pixels of a width x height grid over the embedding, ready for Axes.imshow.
+ *   xy        n_cells x 2 float64 (x, y), CALLER's cell order, n_cells in [1, 2^31)
+ *   V         q x n_cells row-major, 1 <= q <= 16: the value of every cell under every key
+ *   FDR       q x n_cells row-major; row k is read only where has_fdr[k] != 0 (FDR may be NULL when no key has one)
+ *   extent    {x0, x1, y0, y1}.  auto_extent = 0: read; finite with x1 > x0 and y1 > y0.  auto_extent != 0: written, the
+ *             minimum and maximum of x and of y over the cells where both are finite (found on the device, order-free and
+ *             exact); an axis whose minimum equals its maximum v becomes [v - 0.5, v + 0.5], as np.histogram widens it.
+ *             With no such cell at all extent becomes four NaN, the call returns 0 and writes nothing else.
+ *   width, height in [1, 4096] with q * width * height <= 2^22; radius in [0, 16]
+ * The pixel rule.  sx = (double)width / (x1 - x0), sy = (double)height / (y1 - y0), each evaluated once on the host.  A
+ * cell is INSIDE when x and y are finite, x0 <= x <= x1 and y0 <= y <= y1; then t = (x - x0) * sx, one subtraction and one
+ * multiplication each rounded on its own, ix = (int64)floor(t), and x == x1 or a rounded ix >= width give width - 1; iy
+ * likewise from y0, sy and height.  Images are [iy * width + ix], row 0 at y0 (imshow's origin='lower').
+ * A cell PASSES for key k when V[k] is finite and, where has_fdr[k], FDR[k] <= fdr_thresh (a NaN fdr fails).
+ *   n_out[height * width]            inside cells, whatever their values (the grey layer)
+ *   *n_outside_out                   cells with finite coordinates that are not inside
+ *   n_pass_out[q * height * width]   inside cells that pass
+ *   sum_out                          their sum, 0 where none passes
+ *   top_out, bottom_out              their largest (what sort_order=True leaves visible) and smallest value, NaN where
+ *                                    none passes; +0.0 and -0.0 compare equal, which sign comes back is not specified
+ *   absmax_out[q]                    max |V[k]| over the inside cells that pass (vmin / vmax of _umap.py:27-28), NaN if none
+ *   covered_out[height * width]      (may be NULL) 1 where a pixel within the disc (ix - ix')^2 + (iy - iy')^2 <= radius^2
+ *                                    has n > 0, else 0
+ * radius > 0 (the marker size s of the scatter) replaces top_out / bottom_out by their dilations with the same disc: the
+ * maximum of top, the minimum of bottom over the disc's pixels inside the image, pixels where nothing passes ignored.  The
+ * counts and the sums stay per pixel.
+ * Counts, top, bottom, absmax and the extent are exact.  sum is float64 in a fixed order that does not depend on
+ * scheduling (the passing cells of a pixel ascending in the cell index, cut into chunks whose partials are added in chunk
+ * order; no floating-point atomics): two runs give the same bits, and a pixel that holds most of the cells is spread over
+ * as many wavefronts as it has chunks.
+ * Like cna_coef_strata it needs no graph and no resident expression matrix and changes no other state; it may be called
+ * between cna_null_local_launch and cna_null_local_fetch, runs on the expression stream with grow-only buffers of its own
+ * (freed by cna_expr_drop) and returns after that stream has drained.
+ * CNA_EINVAL, with nothing written: a side outside [1, 4096], q outside [1, 16], q * width * height > 2^22, radius outside
+ * [0, 16], n_cells outside [1, 2^31), an explicit extent that is not finite or not increasing. */
+int  cna_coef_raster(cna_ctx* ctx, const double* xy, const double* V, const double* FDR, const int32_t* has_fdr, int q,
+                     int64_t n_cells, double fdr_thresh, double* extent, int auto_extent, int width, int height, int radius,
+                     int64_t* n_out, int64_t* n_outside_out, int64_t* n_pass_out, double* sum_out, double* top_out,
+                     double* bottom_out, uint8_t* covered_out, double* absmax_out);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
