@@ -155,6 +155,9 @@ SIGNATURES = {
     'cna_gram_by': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     'cna_coef_raster': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double,
                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    'cna_graph_components_find': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'cna_graph_components_list': (C.c_int, [c_ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'cna_graph_components_label': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
 }
 
 MAT_NAM, MAT_X, MAT_PROJ = 0, 1, 2
@@ -186,7 +189,9 @@ KERNELS = ['colsum', 'nam_first', 'nam_step', 'batch_kurtosis', 'zero_variance',
            'standardize', 'gram', 'gram_reduce', 'ncorrs', 'null_local', 'obs_counts', 'percell_fdr',
            'project_xb', 'transpose', 'rccl', 'condition', 'global_test', 'nam_step_sparse', 'halo_exchange', 'halo_wait',
            'matrix_bins_sort', 'matrix_bins_sum', 'enrich_positions', 'enrich_extremes', 'expr_cross_by', 'gram_by',
-           'raster_upload', 'raster', 'raster_fetch']
+           'raster_upload', 'raster', 'raster_fetch',
+           'components_upload', 'components_hook', 'components_flatten', 'components_check', 'components_tally',
+           'components_label', 'components_fetch']
 
 _lib = None
 

@@ -105,7 +105,9 @@ static const char* kKernelNames[CNA_K_COUNT] = {
     "standardize", "gram", "gram_reduce", "ncorrs", "null_local", "obs_counts", "percell_fdr",
     "project_xb", "transpose", "rccl", "condition", "global_test", "nam_step_sparse", "halo_exchange", "halo_wait",
     "matrix_bins_sort", "matrix_bins_sum", "enrich_positions", "enrich_extremes", "expr_cross_by", "gram_by",
-    "raster_upload", "raster", "raster_fetch"};
+    "raster_upload", "raster", "raster_fetch",
+    "components_upload", "components_hook", "components_flatten", "components_check", "components_tally", "components_label",
+    "components_fetch"};
 
 // entry points that read or replace the NAM collect a pending walk's verdict first
 #define AUTO_FINISH(c)                                                   \

@@ -1385,6 +1385,44 @@ class Engine(_order.CellOrder):
         out.update(extent=tuple(float(e) for e in ext), n_outside=int(n_outside[0]), covered=covered.view(np.bool_), absmax=absmax)
         return out
 
+    def graph_components(self, codes, min_cells=1, n_classes=None):
+        """Connected components of the resident graph inside classes of cells, on the device (cna_graph_components_find /
+        _list / _label): `codes` int32 per cell in the CALLER's order, a class >= 0 or -1 for none (`n_classes` defaults to
+        the largest code + 1).  Two classed cells share a component when a chain of stored entries joins them, read in
+        either direction, through cells of their class; an entry is an edge whatever its value, a stored zero included.
+        The device reads the codes and writes the labels through its own cell order, so nothing per cell is permuted here.
+        Returns (comp, list, n_components_total): `comp` int32 per cell in the caller's order, the index of the cell's
+        component in `list` or -1; `list` a dict of arrays over the components with at least `min_cells` cells -- 'class'
+        int32, 'size' int64, 'first' int64, the smallest caller cell index -- sorted by class, then size descending, then
+        'first'; `n_components_total` int64 per class, before that filter.  `self.sweeps` holds the hook / flatten / check
+        rounds the call took (1 to 32).  The graph is the one `ensure_graph` left; NAM and X stay as they are.  One rank,
+        replicated view."""
+        if self.nranks != 1 or self.view_local:
+            raise NotImplementedError('graph_components needs every row of the graph on this rank (one rank, replicated view)')
+        if self._graph_key is None:
+            raise ValueError('graph_components: no graph is resident (ensure_graph first)')
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if codes.shape != (int(self.n),):
+            raise ValueError('graph_components: %s codes for %d cells' % (codes.shape, int(self.n)))
+        if n_classes is None:
+            n_classes = int(codes.max(initial=-1)) + 1
+        n_classes = int(n_classes)
+        totals = np.zeros(max(n_classes, 1), dtype=np.int64)
+        kept, sweeps = C.c_int64(0), C.c_int(0)
+        check(self.lib.cna_graph_components_find(self.h, ptr(codes), codes.size, max(n_classes, 1), int(max(min_cells, 1)),
+                                                 C.byref(kept), ptr(totals), C.byref(sweeps)), 'cna_graph_components_find')
+        self.sweeps = int(sweeps.value)
+        K = int(kept.value)
+        cls, size, first = (np.empty(K, dtype=np.int32) for _ in range(3))
+        check(self.lib.cna_graph_components_list(self.h, K, ptr(cls), ptr(size), ptr(first)), 'cna_graph_components_list')
+        order = np.lexsort((first, -size.astype(np.int64), cls))        # the list arrives in no fixed order
+        rank = np.empty(K, dtype=np.int32)
+        rank[order] = np.arange(K, dtype=np.int32)
+        comp = np.empty(codes.size, dtype=np.int32)
+        check(self.lib.cna_graph_components_label(self.h, ptr(rank), K, ptr(comp), codes.size), 'cna_graph_components_label')
+        lst = {'class': cls[order], 'size': size[order].astype(np.int64), 'first': first[order].astype(np.int64)}
+        return comp, lst, totals[:n_classes]
+
     def matrix_to_bins(self, which, codes, W=None, n_bins=None):
         """Weighted per-bin sums over the rows of the resident NAM (MAT_NAM) or of the working matrix X (MAT_X), on the
         device (cna_matrix_to_bins): `codes` int32 per cell in the CALLER's order, -1 = cell left out; `W` q x cells

@@ -5,6 +5,7 @@ from ._genes import gene_corr
 from ._gene_test import gene_test
 from ._strata import coef_strata
 from ._raster import coef_raster
+from ._populations import coef_populations
 from ._gene_strata import gene_corr_strata
 from ._gene_test_strata import gene_test_strata
 from ._nam_strata import nam_strata
@@ -12,6 +13,7 @@ from ._gene_sets import gene_set_enrich, gene_set_test
 
 __all__ = [
     'association',
+    'coef_populations',
     'coef_raster',
     'coef_strata',
     'gene_corr',

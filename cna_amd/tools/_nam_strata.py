@@ -26,6 +26,24 @@ MAX_WEIGHTS = 16
 MAX_SUMS = 4096         # weight columns x levels of one device pass
 
 
+def signed_passes(obs, key, fdr_thresh=None):
+    """(expanded, depleted), one bool per cell: ``obs[key]`` finite and > 0 / < 0, and ``obs[key + '_fdr'] <= fdr_thresh``
+    (default 0.1; a NaN fdr fails) where ``obs`` has that column.  KeyError without ``key``, and for ``fdr_thresh`` without the
+    fdr column.  The rule of ``nam_strata(sign_of=...)`` and of ``coef_populations``."""
+    if key not in obs:
+        raise KeyError(key)
+    fkey = '%s_fdr' % (key,)
+    has_fdr = fkey in obs
+    if not has_fdr and fdr_thresh is not None:
+        raise KeyError(fkey)
+    v = numeric_column(obs, key)
+    with np.errstate(invalid='ignore'):
+        passes = np.isfinite(v)
+        if has_fdr:
+            passes &= numeric_column(obs, fkey) <= (FDR_THRESH if fdr_thresh is None else float(fdr_thresh))
+        return passes & (v > 0), passes & (v < 0)
+
+
 def nam_strata(data, stratification, sid_name, weights=None, sign_of=None, fdr_thresh=None, keep=None,
                return_counts=False, nsteps=None, self_weight=1, engine=None):
     """Samples x levels of ``data.obs[stratification]``: the sum of the NAM over the cells of every level.
@@ -60,18 +78,7 @@ def nam_strata(data, stratification, sid_name, weights=None, sign_of=None, fdr_t
     single = weights is None or isinstance(weights, str)
     names, W = None, None
     if sign_of is not None:
-        if sign_of not in obs:
-            raise KeyError(sign_of)
-        fkey = '%s_fdr' % (sign_of,)
-        has_fdr = fkey in obs
-        if not has_fdr and fdr_thresh is not None:
-            raise KeyError(fkey)
-        v = numeric_column(obs, sign_of)
-        with np.errstate(invalid='ignore'):
-            passes = np.isfinite(v)
-            if has_fdr:
-                passes &= numeric_column(obs, fkey) <= (FDR_THRESH if fdr_thresh is None else float(fdr_thresh))
-            W = np.stack([passes & (v > 0), passes & (v < 0)]).astype(np.float64)
+        W = np.stack(signed_passes(obs, sign_of, fdr_thresh)).astype(np.float64)
         names, single = ['pos', 'neg'], False
     elif weights is not None:
         names = [weights] if isinstance(weights, str) else list(weights)

@@ -69,6 +69,13 @@ enum {
    * dilated images, its waits for the extent and for the chunk counts included; the copies of the images back
    * (csrc/raster.hip) */
   CNA_K_RASTER_UPLOAD, CNA_K_RASTER, CNA_K_RASTER_FETCH,
+  /* cna_graph_components_* on the expression stream: the copy of the classes to the device; per round the hooking of the
+   * entries (in the first round three launches -- entry 0 of every row, entry 1, the rest -- with the two flattenings
+   * between them), the flattening of the trees and the count of entries that still join two trees (its kernels only:
+   * the host's read of that count lies between the rounds); sizes, smallest indices and the compaction of the list; the
+   * label kernel; the copies of the list and of the labels back (csrc/components.hip) */
+  CNA_K_COMPONENTS_UPLOAD, CNA_K_COMPONENTS_HOOK, CNA_K_COMPONENTS_FLATTEN, CNA_K_COMPONENTS_CHECK, CNA_K_COMPONENTS_TALLY,
+  CNA_K_COMPONENTS_LABEL, CNA_K_COMPONENTS_FETCH,
   CNA_K_COUNT
 };
 
@@ -617,7 +624,7 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
- * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by and cna_coef_raster:
+ * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster and cna_graph_components_find:
  * cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
@@ -879,6 +886,35 @@ int  cna_coef_raster(cna_ctx* ctx, const double* xy, const double* V, const doub
                      int64_t n_cells, double fdr_thresh, double* extent, int auto_extent, int width, int height, int radius,
                      int64_t* n_out, int64_t* n_outside_out, int64_t* n_pass_out, double* sum_out, double* top_out,
                      double* bottom_out, uint8_t* covered_out, double* absmax_out);
+
+/* ---- connected populations of the resident graph (csrc/components.hip) ------------------------ */
+/* What the reference's demo says in words after cna.tl.association (demo/demo.ipynb 1.3: "a sub-population of the left-hand
+ * cluster", "these cells comprise only ~6 % of the cells that pass the threshold"), as data: the connected groups of cells
+ * of one class in the kNN graph that cna_graph_upload made resident (_nam.py:12-19 is where the reference reads it).
+ *   codes      int32 per cell, CALLER's cell order: a class in [0, n_classes) or -1 for none; n_cells = the graph's cells
+ * Two classed cells belong to one component when a chain of stored entries joins them, read in either direction, every
+ * cell on the chain being of their class (weak connectivity; self loops and duplicates change nothing).  An entry is an
+ * edge whatever its value, a stored zero included: the values of the graph are not read.
+ * cna_graph_components_find runs a lock-free union-find on the device (hooking by compare-and-swap on roots, path
+ * shortening by atomic minimum, no thread ever waits for another), flattens it and counts the same-class entries whose
+ * ends still have different roots; while that count is not zero it repeats from the current state, 32 rounds at most
+ * (CNA_ESTATE beyond).  Then the size and the smallest caller index of every component by integer atomics.
+ *   *n_kept_out   the components with at least min_cells cells
+ *   totals_out    [n_classes]: the components of every class, before that filter
+ *   *sweeps_out   rounds taken, >= 1
+ * cna_graph_components_list copies the kept components out: class, size, smallest caller cell index, n_kept each, in the
+ * order in which they arrived on the device -- NOT a fixed one: sort them.
+ * cna_graph_components_label writes comp_out[cell] (caller's order, int32): rank[j] for a cell of the component at place j
+ * of that list (rank = NULL: j itself; else a permutation's values in [0, n_kept)), -1 for a cell without a class or of a
+ * component below min_cells.
+ * One rank holding the whole graph (CNA_ESTATE otherwise).  The three read the graph and the device's cell order and
+ * write only buffers of their own (freed by cna_expr_drop, after which _list and _label want a new _find; likewise after
+ * a new graph or cell order): the walk, the NAM, X and everything derived from them stay valid.  They run on the expression
+ * stream behind whatever the main stream has queued and return once their stream has drained.  No floating point. */
+int  cna_graph_components_find(cna_ctx* ctx, const int32_t* codes, int64_t n_cells, int n_classes, int64_t min_cells,
+                               int64_t* n_kept_out, int64_t* totals_out, int* sweeps_out);
+int  cna_graph_components_list(cna_ctx* ctx, int64_t n_kept, int32_t* class_out, int32_t* size_out, int32_t* first_out);
+int  cna_graph_components_label(cna_ctx* ctx, const int32_t* rank, int64_t n_kept, int32_t* comp_out, int64_t n_cells);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
