@@ -4,7 +4,8 @@
 // (nam_bins.hip: the NAM or X by bin, on this stream with this sort), cna_enrichment_extremes (enrich.hip: no matrix at all,
 // this stream and these buffers), cna_expr_cross_by (expr_cross_by.hip), cna_gram_by (gram_by.hip: X alone) and
 // cna_coef_raster (raster.hip: no matrix, this stream, the sort twice); cna_graph_components_* (components.hip) borrows the
-// stream and a slot of buffers and reads the resident graph.  What two of them need is here once:
+// stream and a slot of buffers and reads the resident graph; cna_gene_ranksum_by (expr_ranksum.hip: a ranking of the cells
+// of every gene, with a radix sort of its own on the chunk tables).  What two of them need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared
 //   ExprState       the resident matrix, the stream, and one slot of work buffers per entry point
 //   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins and cna_gene_corr_by, value
@@ -55,7 +56,7 @@ struct ScopedBufs : BufSet {
 
 // ------------------------------------------------------------------ state (cna_ctx::expr)
 enum ExprUser { EXPR_CORR, EXPR_BINS, EXPR_CROSS, EXPR_STRATA, EXPR_CORR_BY, EXPR_MAT_BINS, EXPR_ENRICH, EXPR_CROSS_BY,
-                EXPR_GRAM_BY, EXPR_RASTER, EXPR_COMPONENTS, EXPR_USERS };
+                EXPR_GRAM_BY, EXPR_RASTER, EXPR_COMPONENTS, EXPR_RANKSUM, EXPR_USERS };
 
 struct ExprState {
   hipStream_t st = nullptr;

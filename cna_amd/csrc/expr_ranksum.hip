@@ -1,0 +1,501 @@
+// cna_gene_ranksum_by: twice the Wilcoxon rank sum of every level of a clustering against all other kept cells, for every
+// gene of the resident expression matrix, with the tie term of its normal approximation (cna.tl.gene_markers).  One ranking
+// of the kept cells per gene serves every level: the level's rank sum is the sum of those global midranks over its cells.
+// All results are integers (the tie term a double that holds one), so the device path is tested for equality.
+//
+//   sort_count (expr.h)   checks every code against [-1, n_bins) before anything is written; the sizes of the levels
+//   k_rs_keys_sparse      one workgroup per chunk of a gene's list: every entry -> an order-preserving unsigned key (-0.0
+//                         and a stored zero = the key of +0.0; float64 on all 64 bits) and the level of its cell.  An entry
+//                         of a left-out cell gets the largest key and the level RS_LEFT: it sorts behind the kept ones and
+//                         the rank kernel never reads it.  Counts the kept entries of the gene, flags a kept NaN
+//   k_rs_keys_dense       a 64 x 64 tile of cells x genes through LDS into the same gene-major form: every kept cell is
+//                         present in every gene (so its kept count is m), a left-out cell rides along as above
+//   k_rs_count / k_rs_scan / k_rs_scatter
+//                         a stable LSD radix sort segmented by gene, 8 bits per pass (float32: 4 passes, float64: 8), on the
+//                         chunk tables of build_chunks (dense: a table of the same shape with chunks of RS_DENSE_CHUNK): a
+//                         count per (chunk, digit) in LDS; per gene a scan over its chunks and then over the digits; one wave
+//                         per chunk scatters, lanes with the same digit ranked by lane (k_sort_fill's rule, by ballots), the
+//                         cursors carried from batch to batch: the result does not depend on scheduling
+//   k_rs_rank             one workgroup per gene walks the sorted list in units of RS_UNIT entries, forward for the start s
+//                         of every entry's tie run (a prefix maximum over the run heads, carried across units) and backward
+//                         for its end e (a suffix minimum over the run tails): less = s, lesseq = e.  The implicit zeros of
+//                         the gene-major form, z = m - kept stored entries, join the run of the stored zeros by arithmetic:
+//                         entries above it move up by z, and every level gets (its cells - its stored entries) times the
+//                         zero group's 2 x midrank.  Per-level sums are integer LDS atomics (exact, so their order is
+//                         immaterial); the tie terms t^3 - t are added per thread in list order and folded by a fixed tree
+//
+// The genes go in tiles of whole genes whose keys, levels and their ping-pong copies stay within work_bytes (0:
+// RS_WORK_BYTES); a gene that alone exceeds it is one tile.  The counters of the sort (1 KB per chunk) come on top.
+#include "expr.h"
+
+namespace {
+
+constexpr int RS_MAX_LEVELS = 1024;
+constexpr int64_t RS_WORK_BYTES = 1ll << 30;   // keys + levels + their copies of one tile, when the caller names no budget
+constexpr int64_t RS_DENSE_CHUNK = 1024;       // cells of one gene per sort chunk of the dense form (build_chunks' least)
+constexpr int RS_UNIT = 256;                   // entries of a gene's sorted list the rank kernel takes at a time
+constexpr int RS_TILE = 64;                    // the dense gather's square tile
+constexpr uint16_t RS_LEFT = 0xffff;           // "level" of an entry whose cell is left out
+using CellList = CellListOf<RS_MAX_LEVELS>;
+
+struct RankSumWork : BufSet {
+  CodeSort sort{*this};
+  Buf keyA{*this}, keyB{*this}, lvlA{*this}, lvlB{*this}, cnt{*this}, dbase{*this}, kept{*this}, nanf{*this}, rank2{*this},
+      tie{*this};
+  Buf seg{*this}, chunk_lo{*this}, chunk_gene{*this}, gchunk{*this};   // the dense form's table (the lists have the state's)
+};
+
+// ------------------------------------------------------------------ keys
+// value -> unsigned key in the order of the values; bits alone decide: denormals stay apart whatever the float mode
+template <typename T>
+struct KeyOf;
+template <>
+struct KeyOf<float> {
+  using K = uint32_t;
+  static constexpr K SIGN = 0x80000000u, MAG = 0x7fffffffu, INF = 0x7f800000u;
+  __device__ static K bits(float x) { return __float_as_uint(x); }
+};
+template <>
+struct KeyOf<double> {
+  using K = uint64_t;
+  static constexpr K SIGN = 0x8000000000000000ull, MAG = 0x7fffffffffffffffull, INF = 0x7ff0000000000000ull;
+  __device__ static K bits(double x) { return (K)__double_as_longlong(x); }
+};
+template <typename T>
+__device__ __forceinline__ typename KeyOf<T>::K rs_key(T x, bool* is_nan) {
+  using P = KeyOf<T>;
+  typename P::K b = P::bits(x);
+  *is_nan = (b & P::MAG) > P::INF;
+  if ((b & P::MAG) == 0) b = 0;                         // -0.0 is +0.0
+  return (b & P::SIGN) ? ~b : (b | P::SIGN);
+}
+
+// workgroup = chunk c0 + blockIdx.x of the gene lists; tile arrays are indexed by entry - base
+template <typename T>
+__global__ __launch_bounds__(256) void k_rs_keys_sparse(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
+                                                        const int64_t* __restrict__ gptr, int64_t c0, int64_t chunk_len,
+                                                        const int32_t* __restrict__ gcell, const T* __restrict__ gval,
+                                                        const int32_t* __restrict__ codes, int64_t base,
+                                                        typename KeyOf<T>::K* __restrict__ key, uint16_t* __restrict__ lvl,
+                                                        unsigned int* __restrict__ kept, unsigned int* __restrict__ nanf) {
+  using K = typename KeyOf<T>::K;
+  const int64_t ch = c0 + blockIdx.x;
+  const int32_t g = chunk_gene[ch];
+  const int64_t lo = chunk_lo[ch], end = gptr[g + 1];
+  const int64_t hi = lo + chunk_len < end ? lo + chunk_len : end;
+  unsigned int mine = 0;
+  bool seen_nan = false;
+  for (int64_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
+    const int32_t cd = codes[gcell[e]];
+    K k = ~(K)0;
+    uint16_t l = RS_LEFT;
+    if (cd >= 0) {
+      bool is_nan;
+      k = rs_key<T>(gval[e], &is_nan);
+      l = (uint16_t)cd;
+      seen_nan = seen_nan || is_nan;
+      ++mine;
+    }
+    key[e - base] = k;
+    lvl[e - base] = l;
+  }
+  __shared__ unsigned int tot;
+  if (threadIdx.x == 0) tot = 0;
+  __syncthreads();
+  if (mine) atomicAdd(&tot, mine);
+  if (seen_nan) nanf[g] = 1u;
+  __syncthreads();
+  if (threadIdx.x == 0 && tot) atomicAdd(&kept[g], tot);
+}
+
+// workgroup = RS_TILE cells x RS_TILE genes of the tile [g0, g1): X[cell][gene] in, entry (gene * n + cell) - base out
+template <typename T>
+__global__ __launch_bounds__(256) void k_rs_keys_dense(const T* __restrict__ X, int64_t n, int64_t G, int64_t g0, int64_t g1,
+                                                       const int32_t* __restrict__ codes, int64_t base,
+                                                       typename KeyOf<T>::K* __restrict__ key, uint16_t* __restrict__ lvl,
+                                                       unsigned int* __restrict__ nanf) {
+  using K = typename KeyOf<T>::K;
+  __shared__ K tk[RS_TILE][RS_TILE + 1];
+  __shared__ uint16_t tl[RS_TILE];
+  const int tx = threadIdx.x % RS_TILE, ty = threadIdx.x / RS_TILE;
+  const int64_t cell0 = (int64_t)blockIdx.x * RS_TILE, gene0 = g0 + (int64_t)blockIdx.y * RS_TILE;
+  if (threadIdx.x < RS_TILE) {
+    const int64_t i = cell0 + threadIdx.x;
+    const int32_t cd = i < n ? codes[i] : -1;
+    tl[threadIdx.x] = cd >= 0 ? (uint16_t)cd : RS_LEFT;
+  }
+  __syncthreads();
+  for (int r = ty; r < RS_TILE; r += 256 / RS_TILE) {
+    const int64_t i = cell0 + r, g = gene0 + tx;
+    K k = ~(K)0;
+    if (i < n && g < g1 && tl[r] != RS_LEFT) {
+      bool is_nan;
+      k = rs_key<T>(X[i * G + g], &is_nan);
+      if (is_nan) nanf[g] = 1u;
+    }
+    tk[r][tx] = k;
+  }
+  __syncthreads();
+  for (int r = ty; r < RS_TILE; r += 256 / RS_TILE) {
+    const int64_t g = gene0 + r, i = cell0 + tx;
+    if (g < g1 && i < n) {
+      key[g * n + i - base] = tk[tx][r];
+      lvl[g * n + i - base] = tl[tx];
+    }
+  }
+}
+
+// ------------------------------------------------------------------ the sort: one pass of 8 bits
+// cnt[chunk - c0][digit] = entries of the chunk with that digit
+template <typename K>
+__global__ __launch_bounds__(256) void k_rs_count(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
+                                                  const int64_t* __restrict__ seg, int64_t c0, int64_t chunk_len, int64_t base,
+                                                  const K* __restrict__ key, int shift, unsigned int* __restrict__ cnt) {
+  __shared__ unsigned int h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t ch = c0 + blockIdx.x;
+  const int64_t lo = chunk_lo[ch], end = seg[chunk_gene[ch] + 1];
+  const int64_t hi = lo + chunk_len < end ? lo + chunk_len : end;
+  for (int64_t e = lo + threadIdx.x; e < hi; e += blockDim.x) atomicAdd(&h[(unsigned)(key[e - base] >> shift) & 255u], 1u);
+  __syncthreads();
+  cnt[(int64_t)blockIdx.x * 256 + threadIdx.x] = h[threadIdx.x];
+}
+
+// workgroup = gene g0 + blockIdx.x, thread = digit: cnt -> the entries of the gene with that digit in the chunks before;
+// dbase[gene - g0][digit] = the gene's entries with a smaller digit
+__global__ __launch_bounds__(256) void k_rs_scan(const int64_t* __restrict__ gchunk, int64_t g0, int64_t c0,
+                                                 unsigned int* __restrict__ cnt, unsigned int* __restrict__ dbase) {
+  __shared__ unsigned int tot[256];
+  const int64_t g = g0 + blockIdx.x;
+  unsigned int run = 0;
+  for (int64_t ch = gchunk[g] - c0; ch < gchunk[g + 1] - c0; ++ch) {
+    const unsigned int t = cnt[ch * 256 + threadIdx.x];
+    cnt[ch * 256 + threadIdx.x] = run;
+    run += t;
+  }
+  tot[threadIdx.x] = run;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int acc = 0;
+    for (int d = 0; d < 256; ++d) {
+      const unsigned int t = tot[d];
+      tot[d] = acc;
+      acc += t;
+    }
+  }
+  __syncthreads();
+  dbase[(int64_t)blockIdx.x * 256 + threadIdx.x] = tot[threadIdx.x];
+}
+
+// one wave per chunk; cur[digit] = where the chunk's next entry with that digit goes inside the gene's segment.  In a batch
+// of 64 entries the lanes with one digit find each other with 8 ballots and take consecutive places in lane order.
+template <typename K>
+__global__ __launch_bounds__(64) void k_rs_scatter(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
+                                                   const int64_t* __restrict__ seg, int64_t c0, int64_t chunk_len, int64_t base,
+                                                   int64_t g0, const K* __restrict__ kin, const uint16_t* __restrict__ lin,
+                                                   K* __restrict__ kout, uint16_t* __restrict__ lout, int shift,
+                                                   const unsigned int* __restrict__ cnt, const unsigned int* __restrict__ dbase) {
+  __shared__ unsigned int cur[256];
+  const int lane = threadIdx.x;
+  const int64_t ch = c0 + blockIdx.x;
+  const int32_t g = chunk_gene[ch];
+  for (int d = lane; d < 256; d += 64) cur[d] = cnt[(int64_t)blockIdx.x * 256 + d] + dbase[(int64_t)(g - g0) * 256 + d];
+  __syncthreads();
+  const int64_t lo = chunk_lo[ch], end = seg[g + 1], at = seg[g] - base;
+  const int64_t hi = lo + chunk_len < end ? lo + chunk_len : end;
+  for (int64_t e0 = lo; e0 < hi; e0 += 64) {
+    const int64_t e = e0 + lane;
+    const bool valid = e < hi;
+    K k = 0;
+    uint16_t l = 0;
+    if (valid) {
+      k = kin[e - base];
+      l = lin[e - base];
+    }
+    const unsigned int d = (unsigned)(k >> shift) & 255u;
+    unsigned long long same = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b & 1u) != 0;
+      const unsigned long long bal = __ballot(valid && bit);
+      same &= bit ? bal : ~bal;
+    }
+    const unsigned int rank = (unsigned)__popcll(same & ((1ull << lane) - 1ull));
+    const bool last = (same >> lane) == 1ull;
+    if (valid) {
+      const int64_t to = at + (int64_t)(cur[d] + rank);
+      kout[to] = k;
+      lout[to] = l;
+    }
+    __syncthreads();
+    if (valid && last) cur[d] += rank + 1u;
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------ ranks
+// inclusive scan over the 256 threads: the maximum of v over the threads up to this one (rev: from this one on)
+__device__ __forceinline__ long long rs_scan_max(long long v, long long* sh, bool rev) {
+  const int t = rev ? RS_UNIT - 1 - (int)threadIdx.x : (int)threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int o = 1; o < RS_UNIT; o <<= 1) {
+    const long long x = t >= o ? sh[t - o] : v;
+    __syncthreads();
+    if (x > v) v = x;
+    sh[t] = v;
+    __syncthreads();
+  }
+  return v;
+}
+
+// workgroup = gene g0 + blockIdx.x over its kept[g] sorted entries; nlev[b]: cells of level b; m: kept cells
+template <typename K>
+__global__ __launch_bounds__(RS_UNIT) void k_rs_rank(const K* __restrict__ key, const uint16_t* __restrict__ lvl,
+                                                     const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,
+                                                     const unsigned int* __restrict__ kept, const int64_t* __restrict__ nlev,
+                                                     int64_t m, int n_bins, long long* __restrict__ rank2,
+                                                     double* __restrict__ tie) {
+  constexpr K K0 = (K)1 << (8 * sizeof(K) - 1);       // the key of +0.0
+  __shared__ unsigned long long sum[RS_MAX_LEVELS];
+  __shared__ unsigned int stored[RS_MAX_LEVELS];
+  __shared__ long long sh[RS_UNIT];
+  __shared__ double tsh[RS_UNIT];
+  __shared__ unsigned int below, zeros;
+  const int t = threadIdx.x;
+  const int64_t g = g0 + blockIdx.x;
+  const long long k = (long long)kept[g], z = (long long)m - k;
+  key += seg[g] - base;
+  lvl += seg[g] - base;
+  for (int b = t; b < n_bins; b += RS_UNIT) {
+    sum[b] = 0;
+    stored[b] = 0;
+  }
+  if (t == 0) below = zeros = 0;
+  __syncthreads();
+  // forward: s = the first entry of the run an entry lies in
+  double tacc = 0.0;
+  unsigned int my_below = 0, my_zeros = 0;
+  long long carry = 0;
+  for (long long u0 = 0; u0 < k; u0 += RS_UNIT) {
+    const long long p = u0 + t;
+    const bool valid = p < k;
+    K kk = 0;
+    bool head = false, tail = false;
+    if (valid) {
+      kk = key[p];
+      head = p == 0 || key[p - 1] != kk;
+      tail = p == k - 1 || key[p + 1] != kk;
+    }
+    const long long s = rs_scan_max(head ? p : (t == 0 ? carry : -1), sh, false);
+    carry = sh[RS_UNIT - 1];
+    if (valid) {
+      const unsigned int l = lvl[p];
+      if (l < (unsigned)n_bins) {                     // (only a gene with a kept NaN can show RS_LEFT here)
+        atomicAdd(&sum[l], (unsigned long long)(s + (kk > K0 ? z : 0)));
+        atomicAdd(&stored[l], 1u);
+      }
+      my_below += kk < K0 ? 1u : 0u;
+      my_zeros += kk == K0 ? 1u : 0u;
+      if (tail && kk != K0) {
+        const long long r = p + 1 - s;
+        tacc += (double)r * (double)(r * r - 1);
+      }
+    }
+    __syncthreads();                                  // sh is read (carry) before the next scan writes it
+  }
+  // backward: e = one past the last entry of the run
+  carry = 0;
+  for (long long u0 = k > 0 ? (k - 1) / RS_UNIT * RS_UNIT : -1; u0 >= 0; u0 -= RS_UNIT) {
+    const long long p = u0 + t;
+    const bool valid = p < k;
+    K kk = 0;
+    bool tail = false;
+    if (valid) {
+      kk = key[p];
+      tail = p == k - 1 || key[p + 1] != kk;
+    }
+    // the minimum of the run ends from here on, as a maximum of their negatives; the last thread of a full unit carries
+    const long long none = -0x7fffffffffffffffll;
+    const long long e = -rs_scan_max(tail ? -(p + 1) : (valid && t == RS_UNIT - 1 ? carry : none), sh, true);
+    carry = sh[RS_UNIT - 1];                          // reversed index: thread 0's value, negated as it is used
+    if (valid) {
+      const unsigned int l = lvl[p];
+      if (l < (unsigned)n_bins) atomicAdd(&sum[l], (unsigned long long)(e + (kk >= K0 ? z : 0)));
+    }
+    __syncthreads();
+  }
+  if (my_below) atomicAdd(&below, my_below);
+  if (my_zeros) atomicAdd(&zeros, my_zeros);
+  tsh[t] = tacc;
+  __syncthreads();
+  for (int w = RS_UNIT / 2; w > 0; w >>= 1) {
+    if (t < w) tsh[t] += tsh[t + w];
+    __syncthreads();
+  }
+  const long long t0 = (long long)zeros + z;          // the zero group: stored and implicit zeros
+  if (t == 0) tie[g] = tsh[0] + (t0 > 0 ? (double)t0 * (double)(t0 * t0 - 1) : 0.0);
+  for (int b = t; b < n_bins; b += RS_UNIT) {
+    const long long st = (long long)stored[b];
+    rank2[(int64_t)b * G + g] = (long long)sum[b] + st + ((long long)nlev[b] - st) * (2 * (long long)below + t0 + 1);
+  }
+}
+
+// a chunk table of the lists' shape for the dense form: gene g holds the entries [g n, (g + 1) n)
+int dense_table(cna_ctx* c, ExprState* s, RankSumWork* w, std::vector<int64_t>& seg_h, std::vector<int64_t>& gchunk_h) {
+  const int64_t n = s->n, G = s->G, per = (n + RS_DENSE_CHUNK - 1) / RS_DENSE_CHUNK;
+  std::vector<int64_t> lo((size_t)(G * per));
+  std::vector<int32_t> gene((size_t)(G * per));
+  seg_h.resize((size_t)G + 1);
+  gchunk_h.resize((size_t)G + 1);
+  for (int64_t g = 0; g <= G; ++g) {
+    seg_h[(size_t)g] = g * n;
+    gchunk_h[(size_t)g] = g * per;
+  }
+  for (int64_t g = 0; g < G; ++g)
+    for (int64_t j = 0; j < per; ++j) {
+      lo[(size_t)(g * per + j)] = g * n + j * RS_DENSE_CHUNK;
+      gene[(size_t)(g * per + j)] = (int32_t)g;
+    }
+  CNA_TRY(buf_need(c, s->st, w->seg, 8 * (G + 1)));
+  CNA_TRY(buf_need(c, s->st, w->gchunk, 8 * (G + 1)));
+  CNA_TRY(buf_need(c, s->st, w->chunk_lo, 8 * G * per));
+  CNA_TRY(buf_need(c, s->st, w->chunk_gene, 4 * G * per));
+  HIP_TRY(hipMemcpyAsync(w->seg.p, seg_h.data(), 8 * (size_t)(G + 1), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemcpyAsync(w->gchunk.p, gchunk_h.data(), 8 * (size_t)(G + 1), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemcpyAsync(w->chunk_lo.p, lo.data(), 8 * lo.size(), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemcpyAsync(w->chunk_gene.p, gene.data(), 4 * gene.size(), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));               // the host vectors end with this scope
+  return 0;
+}
+
+template <typename T>
+int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t work_bytes, int64_t m) {
+  using K = typename KeyOf<T>::K;
+  const int64_t n = s->n, G = s->G;
+  const bool dense = s->format == 1;
+  std::vector<int64_t> seg_h, gchunk_own;
+  const int64_t *seg, *chunk_lo, *gchunk;
+  const int32_t* chunk_gene;
+  int64_t chunk_len;
+  if (dense) {
+    CNA_TRY(dense_table(c, s, w, seg_h, gchunk_own));
+    seg = w->seg.as<const int64_t>();
+    chunk_lo = w->chunk_lo.as<const int64_t>();
+    chunk_gene = w->chunk_gene.as<const int32_t>();
+    gchunk = w->gchunk.as<const int64_t>();
+    chunk_len = RS_DENSE_CHUNK;
+  } else {
+    seg_h.resize((size_t)G + 1);
+    HIP_TRY(hipMemcpyAsync(seg_h.data(), s->gptr.p, 8 * (size_t)(G + 1), hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+    seg = s->gptr.as<const int64_t>();
+    chunk_lo = s->chunk_lo.as<const int64_t>();
+    chunk_gene = s->chunk_gene.as<const int32_t>();
+    gchunk = s->gchunk.as<const int64_t>();
+    chunk_len = s->chunk_len;
+  }
+  const std::vector<int64_t>& gchunk_h = dense ? gchunk_own : s->gchunk_h;
+  // tiles of whole genes: keys, levels and their copies within the budget
+  const int64_t per_entry = 2 * ((int64_t)sizeof(K) + 2);
+  const int64_t max_entries = std::max<int64_t>(1, (work_bytes > 0 ? work_bytes : RS_WORK_BYTES) / per_entry);
+  std::vector<GeneTile> tiles;
+  int64_t most_entries = 1, most_chunks = 1, most_genes = 1;
+  for (int64_t g0 = 0, g1; g0 < G; g0 = g1) {
+    g1 = g0 + 1;
+    while (g1 < G && seg_h[(size_t)g1 + 1] - seg_h[(size_t)g0] <= max_entries) ++g1;
+    tiles.push_back({g0, g1, gchunk_h[(size_t)g0], gchunk_h[(size_t)g1] - gchunk_h[(size_t)g0]});
+    most_entries = std::max(most_entries, seg_h[(size_t)g1] - seg_h[(size_t)g0]);
+    most_chunks = std::max(most_chunks, tiles.back().nch);
+    most_genes = std::max(most_genes, g1 - g0);
+  }
+  if (most_chunks > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_by: more than 2^31 - 1 chunks in one tile of genes");
+  CNA_TRY(buf_need(c, s->st, w->keyA, (int64_t)sizeof(K) * most_entries));
+  CNA_TRY(buf_need(c, s->st, w->keyB, (int64_t)sizeof(K) * most_entries));
+  CNA_TRY(buf_need(c, s->st, w->lvlA, 2 * most_entries));
+  CNA_TRY(buf_need(c, s->st, w->lvlB, 2 * most_entries));
+  CNA_TRY(buf_need(c, s->st, w->cnt, 4 * 256 * most_chunks));
+  CNA_TRY(buf_need(c, s->st, w->dbase, 4 * 256 * most_genes));
+  CNA_TRY(buf_need(c, s->st, w->kept, 4 * G));
+  CNA_TRY(buf_need(c, s->st, w->nanf, 4 * G));
+  CNA_TRY(buf_need(c, s->st, w->rank2, 8 * (int64_t)n_bins * G));
+  CNA_TRY(buf_need(c, s->st, w->tie, 8 * G));
+  HIP_TRY(hipMemsetAsync(w->nanf.p, 0, (size_t)(4 * G), s->st));
+  if (dense) {
+    std::vector<unsigned int> all((size_t)G, (unsigned int)m);    // every kept cell is present in every gene
+    HIP_TRY(hipMemcpyAsync(w->kept.p, all.data(), (size_t)(4 * G), hipMemcpyHostToDevice, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+  } else {
+    HIP_TRY(hipMemsetAsync(w->kept.p, 0, (size_t)(4 * G), s->st));
+  }
+  K *ka = w->keyA.as<K>(), *kb = w->keyB.as<K>();
+  uint16_t *la = w->lvlA.as<uint16_t>(), *lb = w->lvlB.as<uint16_t>();
+  unsigned int *cnt = w->cnt.as<unsigned int>(), *dbase = w->dbase.as<unsigned int>();
+  for (const GeneTile& t : tiles) {
+    const int64_t base = seg_h[(size_t)t.g0];
+    const unsigned genes = (unsigned)(t.g1 - t.g0);
+    if (t.nch) {
+      {
+        ProfScope ps(c, CNA_K_RANKSUM_KEYS, s->st);
+        if (dense)
+          hipLaunchKernelGGL(k_rs_keys_dense<T>, dim3((unsigned)((n + RS_TILE - 1) / RS_TILE), (genes + RS_TILE - 1) / RS_TILE),
+                             dim3(256), 0, s->st, s->X.as<const T>(), n, G, t.g0, t.g1, w->sort.codes(), base, ka, la,
+                             w->nanf.as<unsigned int>());
+        else
+          hipLaunchKernelGGL(k_rs_keys_sparse<T>, dim3((unsigned)t.nch), dim3(256), 0, s->st, chunk_lo, chunk_gene, seg, t.c0,
+                             chunk_len, s->gcell.as<const int32_t>(), s->gval.as<const T>(), w->sort.codes(), base, ka, la,
+                             w->kept.as<unsigned int>(), w->nanf.as<unsigned int>());
+      }
+      ProfScope ps(c, CNA_K_RANKSUM_SORT, s->st);
+      for (int pass = 0; pass < (int)sizeof(K); ++pass) {         // an even number of passes: the result is in A again
+        const int shift = 8 * pass;
+        hipLaunchKernelGGL(k_rs_count<K>, dim3((unsigned)t.nch), dim3(256), 0, s->st, chunk_lo, chunk_gene, seg, t.c0, chunk_len,
+                           base, (const K*)ka, shift, cnt);
+        hipLaunchKernelGGL(k_rs_scan, dim3(genes), dim3(256), 0, s->st, gchunk, t.g0, t.c0, cnt, dbase);
+        hipLaunchKernelGGL(k_rs_scatter<K>, dim3((unsigned)t.nch), dim3(64), 0, s->st, chunk_lo, chunk_gene, seg, t.c0, chunk_len,
+                           base, t.g0, (const K*)ka, (const uint16_t*)la, kb, lb, shift, (const unsigned int*)cnt,
+                           (const unsigned int*)dbase);
+        std::swap(ka, kb);
+        std::swap(la, lb);
+      }
+    }
+    ProfScope ps(c, CNA_K_RANKSUM_RANK, s->st);
+    hipLaunchKernelGGL(k_rs_rank<K>, dim3(genes), dim3(RS_UNIT), 0, s->st, (const K*)ka, (const uint16_t*)la, seg, base, t.g0, G,
+                       w->kept.as<const unsigned int>(), w->sort.tot.as<const int64_t>(), m, n_bins, w->rank2.as<long long>(),
+                       w->tie.as<double>());
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cna_gene_ranksum_by(cna_ctx* c, const int32_t* codes, int n_bins, int64_t work_bytes, int64_t* rank2_out,
+                                   double* tie_out, int64_t* n_out, uint8_t* nan_out) {
+  CHECK_CTX(c);
+  ExprState* s = expr_state(c);
+  if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_gene_ranksum_by: no expression matrix is resident (cna_expr_upload_*)");
+  if (!codes || !rank2_out || !tie_out || !n_out || !nan_out) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_by: null pointer");
+  if (n_bins < 1 || n_bins > RS_MAX_LEVELS) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_by: 1 <= n_bins <= 1024");
+  if (work_bytes < 0) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_by: work_bytes is 0 (the default) or a number of bytes");
+  const int64_t G = s->G;
+  RankSumWork* w = expr_work<RankSumWork>(s, EXPR_RANKSUM);
+  // the codes are judged before anything is written; the sizes of the levels
+  CNA_TRY(sort_count(c, s->st, w->sort, CellList{}, codes, s->n, n_bins, 0, 2,
+                     "cna_gene_ranksum_by: a code lies outside [-1, n_bins)"));
+  int64_t m = 0;
+  for (int b = 0; b < n_bins; ++b) m += w->sort.tot_h[(size_t)b];
+  if (s->is_f64) CNA_TRY(ranksum_run<double>(c, s, w, n_bins, work_bytes, m));
+  else CNA_TRY(ranksum_run<float>(c, s, w, n_bins, work_bytes, m));
+  std::vector<unsigned int> nanf((size_t)G);
+  {
+    ProfScope ps(c, CNA_K_RANKSUM_FETCH, s->st);
+    CNA_TRY(fetch_results(s->st, "cna_gene_ranksum_by", {{rank2_out, w->rank2.p, (size_t)(8 * (int64_t)n_bins * G)},
+                                                        {tie_out, w->tie.p, (size_t)(8 * G)},
+                                                        {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
+  }
+  for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
+  for (int b = 0; b < n_bins; ++b) n_out[b] = w->sort.tot_h[(size_t)b];
+  return 0;
+}

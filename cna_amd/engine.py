@@ -1327,6 +1327,25 @@ class Engine(_order.CellOrder):
                                         ptr(n)), 'cna_gene_corr_by')
         return r, within, n
 
+    def gene_ranksum_by(self, codes, n_levels, work_bytes=0):
+        """Twice the rank sum of every level of `codes` (int32 per cell, -1 = cell left out) against all kept cells, for
+        every gene of the resident expression matrix, midranks over the kept cells (cna_gene_ranksum_by).  `work_bytes`
+        bounds the sort's keys of one tile of genes (0: the library's default).  Returns (rank2 int64[n_levels, genes],
+        tie float64[genes]: sum of t^3 - t over the tie groups, n int64[n_levels]: cells per level, nan bool[genes]: a kept
+        cell holds NaN and the gene's numbers mean nothing)."""
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        info = self.expression_shape()
+        if info['format'] != 'none' and codes.shape != (info['n_cells'],):
+            raise ValueError('gene_ranksum_by: %d codes for %d resident cells' % (codes.size, info['n_cells']))
+        n_levels = int(n_levels)
+        rank2 = np.empty((max(n_levels, 0), info['n_genes']), dtype=np.int64)
+        tie = np.empty(info['n_genes'])
+        n = np.empty(max(n_levels, 0), dtype=np.int64)
+        nan = np.empty(info['n_genes'], dtype=np.uint8)
+        check(self.lib.cna_gene_ranksum_by(self.h, ptr(codes), n_levels, int(work_bytes), ptr(rank2), ptr(tie), ptr(n),
+                                           ptr(nan)), 'cna_gene_ranksum_by')
+        return rank2, tie, n, nan.astype(bool)
+
     BW_KINDS = ('scott', 'silverman', 'constant')
 
     def coef_strata(self, v, fdr, codes, n_bins, fdr_thresh, points, bw_kind='scott', bw_value=0.0):

@@ -8,6 +8,7 @@ from ._raster import coef_raster
 from ._populations import coef_populations
 from ._gene_strata import gene_corr_strata
 from ._gene_test_strata import gene_test_strata
+from ._gene_markers import gene_markers
 from ._nam_strata import nam_strata
 from ._gene_sets import gene_set_enrich, gene_set_test
 
@@ -18,6 +19,7 @@ __all__ = [
     'coef_strata',
     'gene_corr',
     'gene_corr_strata',
+    'gene_markers',
     'gene_set_enrich',
     'gene_set_test',
     'gene_test',

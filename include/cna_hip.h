@@ -76,6 +76,9 @@ enum {
    * label kernel; the copies of the list and of the labels back (csrc/components.hip) */
   CNA_K_COMPONENTS_UPLOAD, CNA_K_COMPONENTS_HOOK, CNA_K_COMPONENTS_FLATTEN, CNA_K_COMPONENTS_CHECK, CNA_K_COMPONENTS_TALLY,
   CNA_K_COMPONENTS_LABEL, CNA_K_COMPONENTS_FETCH,
+  /* cna_gene_ranksum_by on the expression stream: the keys and levels of a tile of genes; the passes of the radix sort;
+   * the rank kernel; the copies of the results back (csrc/expr_ranksum.hip) */
+  CNA_K_RANKSUM_KEYS, CNA_K_RANKSUM_SORT, CNA_K_RANKSUM_RANK, CNA_K_RANKSUM_FETCH,
   CNA_K_COUNT
 };
 
@@ -624,8 +627,8 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
- * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster and cna_graph_components_find:
- * cna_ctx_device_bytes returns to what it was before the upload. */
+ * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster, cna_graph_components_find and
+ * cna_gene_ranksum_by: cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -716,6 +719,35 @@ int  cna_coef_strata(cna_ctx* ctx, const double* v, const double* fdr, const int
  * outside [-1, n_bins) -- found on the device before any sum is formed. */
 int  cna_gene_corr_by(cna_ctx* ctx, const double* V, int q, const int32_t* codes, int n_bins, double* r_out,
                       double* within_out, int64_t* n_out);
+
+/* ---- exact rank sums of every level against the rest, per gene (csrc/expr_ranksum.hip) -------- */
+/* The question after cna.tl.coef_populations (or sc.tl.leiden) has named groups of cells: which genes mark each group
+ * against all other cells?  The statistic is the Wilcoxon rank sum / Mann-Whitney U of scanpy's
+ * rank_genes_groups(method='wilcoxon'); it needs a ranking of the CELLS of every gene, and one ranking over all kept
+ * cells serves every level: the level's rank sum is the sum of those ranks over its cells.
+ *   codes[i]  the level of cell i (CALLER's cell order), -1 for a cell that is left out; 1 <= n_bins <= 1024
+ *   work_bytes  what the keys, the levels and their ping-pong copies of one tile of whole genes may take; 0: 1 GiB.  A
+ *             gene that alone exceeds it is one tile.  The sort's counters (1 KB per chunk of a gene's list) come on top
+ * The m kept cells are those with a code >= 0.  Per gene g the kept cells are ranked by x[i,g] with midranks: less(i)
+ * and lesseq(i) count the kept cells with a smaller / a not larger value.
+ *   rank2_out[b * n_genes + g] = sum over the cells of level b of less + lesseq + 1: twice the rank sum, <= m (m + 1)
+ *   tie_out[g] = sum over the tie groups of t^3 - t, each term (double)t * (double)(t * t - 1) with t * t - 1 in 64-bit
+ *   integers, added in a fixed order: exact whenever the total is below 2^53, the same bits on every run and for a CSR
+ *   and a CSC upload of one matrix
+ *   n_out[b] = cells of level b
+ *   nan_out[g] = 1 when a KEPT cell holds NaN in gene g (the gene's other outputs are then unspecified); a NaN in a
+ *   left-out cell sets nothing
+ * Order is by value: +-inf are ordinary values, -0.0 equals +0.0, a stored zero of a sparse upload equals the implicit
+ * ones, and a float64 matrix is ranked on all 64 bits (two values that round to one float32 are no tie).
+ * A stable LSD radix sort segmented by gene (8 bits per pass: 4 passes for float32, 8 for float64) orders {key, level};
+ * on the gene-major form only the stored entries are sorted, the implicit zeros are one tie group placed by arithmetic.
+ * Like its siblings it runs on the expression stream with grow-only buffers of its own (freed by cna_expr_drop), changes
+ * no other state, works on a context that never saw a graph and may be called between cna_null_local_launch and
+ * cna_null_local_fetch.
+ * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL, with nothing written: n_bins or work_bytes out of range,
+ * or a code outside [-1, n_bins) -- found on the device before anything else runs. */
+int  cna_gene_ranksum_by(cna_ctx* ctx, const int32_t* codes, int n_bins, int64_t work_bytes, int64_t* rank2_out,
+                         double* tie_out, int64_t* n_out, uint8_t* nan_out);
 
 /* ---- the expression matrix against the working matrix (csrc/expr_cross.hip) ------------------- */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
