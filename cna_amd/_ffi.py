@@ -147,6 +147,8 @@ SIGNATURES = {
                                   C.c_double] + [C.c_void_p] * 10),
     'cna_gene_corr_by': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cna_gene_ranksum_by': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'cna_gene_ranksum_pairs': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     'cna_x_generation': (C.c_int, [c_ctx, C.POINTER(C.c_int64)]),
     'cna_matrix_to_bins': (C.c_int, [c_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     'cna_enrichment_extremes': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -192,7 +194,8 @@ KERNELS = ['colsum', 'nam_first', 'nam_step', 'batch_kurtosis', 'zero_variance',
            'matrix_bins_sort', 'matrix_bins_sum', 'enrich_positions', 'enrich_extremes', 'expr_cross_by', 'gram_by',
            'raster_upload', 'raster', 'raster_fetch',
            'components_upload', 'components_hook', 'components_flatten', 'components_check', 'components_tally',
-           'components_label', 'components_fetch', 'ranksum_keys', 'ranksum_sort', 'ranksum_rank', 'ranksum_fetch']
+           'components_label', 'components_fetch', 'ranksum_keys', 'ranksum_sort', 'ranksum_rank', 'ranksum_fetch',
+           'ranksum_pairs']
 
 _lib = None
 

@@ -107,7 +107,8 @@ static const char* kKernelNames[CNA_K_COUNT] = {
     "matrix_bins_sort", "matrix_bins_sum", "enrich_positions", "enrich_extremes", "expr_cross_by", "gram_by",
     "raster_upload", "raster", "raster_fetch",
     "components_upload", "components_hook", "components_flatten", "components_check", "components_tally", "components_label",
-    "components_fetch", "ranksum_keys", "ranksum_sort", "ranksum_rank", "ranksum_fetch"};
+    "components_fetch", "ranksum_keys", "ranksum_sort", "ranksum_rank", "ranksum_fetch",
+    "ranksum_pairs"};
 
 // entry points that read or replace the NAM collect a pending walk's verdict first
 #define AUTO_FINISH(c)                                                   \

@@ -24,6 +24,12 @@
 //                         zero group's 2 x midrank.  Per-level sums are integer LDS atomics (exact, so their order is
 //                         immaterial); the tie terms t^3 - t are added per thread in list order and folded by a fixed tree
 //
+// cna_gene_ranksum_pairs: one level against another (cna.tl.gene_markers_pairs) from the same sort -- order within the union
+// of two levels is the order within all kept cells.  ranksum_sorted is the part both entries share (tiles, keys, passes);
+//   k_rs_pairs            behind it, one workgroup per gene, forward only: per-level prefix counts of the unit from wave
+//                         ballots, so that every tie run knows its cells per level and those below it; 2 U and the tie term
+//                         of every unordered pair of at most 64 levels in integer accumulators in LDS (stated at the kernel)
+//
 // The genes go in tiles of whole genes whose keys, levels and their ping-pong copies stay within work_bytes (0:
 // RS_WORK_BYTES); a gene that alone exceeds it is one tile.  The counters of the sort (1 KB per chunk) come on top.
 #include "expr.h"
@@ -36,12 +42,19 @@ constexpr int64_t RS_DENSE_CHUNK = 1024;       // cells of one gene per sort chu
 constexpr int RS_UNIT = 256;                   // entries of a gene's sorted list the rank kernel takes at a time
 constexpr int RS_TILE = 64;                    // the dense gather's square tile
 constexpr uint16_t RS_LEFT = 0xffff;           // "level" of an entry whose cell is left out
+constexpr int RP_MAX_LEVELS = 64;              // cna_gene_ranksum_pairs: levels that take part,
+constexpr int RP_SLOTS = 2016;                 // their unordered pairs (the accumulators in LDS) and
+constexpr int RP_MAX_PAIRS = 2016;             // the pairs of one call
+constexpr int RP_BIG = 16;                     // a tie run of this many entries is added by the whole workgroup
+constexpr int RP_BIG_MOST = RS_UNIT / RP_BIG + 1;   // such runs that can end in one unit: one from before, the rest inside
+static_assert(RP_SLOTS == RP_MAX_LEVELS * (RP_MAX_LEVELS - 1) / 2, "one slot per unordered pair of levels");
 using CellList = CellListOf<RS_MAX_LEVELS>;
 
 struct RankSumWork : BufSet {
   CodeSort sort{*this};
   Buf keyA{*this}, keyB{*this}, lvlA{*this}, lvlB{*this}, cnt{*this}, dbase{*this}, kept{*this}, nanf{*this}, rank2{*this},
       tie{*this};
+  Buf pairs{*this}, u2{*this}, ptie{*this};                            // cna_gene_ranksum_pairs: its pairs and results
   Buf seg{*this}, chunk_lo{*this}, chunk_gene{*this}, gchunk{*this};   // the dense form's table (the lists have the state's)
 };
 
@@ -342,6 +355,227 @@ __global__ __launch_bounds__(RS_UNIT) void k_rs_rank(const K* __restrict__ key, 
   }
 }
 
+// ------------------------------------------------------------------ level against level
+// 128-bit sums as {low 64 bits, what lies above}: a tie term t^3 - t of up to 2^31 cells passes 2^64
+struct U128 {
+  unsigned long long lo, hi;
+};
+__device__ __forceinline__ U128 u128_mul(unsigned long long a, unsigned long long b) { return {a * b, __umul64hi(a, b)}; }
+__device__ __forceinline__ U128 u128_add(U128 a, U128 b) {
+  const unsigned long long lo = a.lo + b.lo;
+  return {lo, a.hi + b.hi + (lo < a.lo ? 1ull : 0ull)};
+}
+__device__ __forceinline__ U128 rp_tie_term(unsigned long long t) { return t ? u128_mul(t * t - 1ull, t) : U128{0ull, 0ull}; }
+// an exact, commutative add in LDS: the carry out of the low word is that of this add in whatever order the adds land
+__device__ __forceinline__ void rp_add128(unsigned long long* lo, unsigned int* hi, U128 x) {
+  if (!(x.lo | x.hi)) return;
+  const unsigned long long old = atomicAdd(lo, x.lo);
+  const unsigned int up = (unsigned int)x.hi + (old + x.lo < old ? 1u : 0u);
+  if (up) atomicAdd(hi, up);
+}
+// the accumulators are kept per unordered pair a < b
+__device__ __forceinline__ int rp_slot(int a, int b) { return b * (b - 1) / 2 + a; }
+
+// workgroup = gene g0 + blockIdx.x over its kept[g] sorted entries, RS_UNIT at a time, forward only.  With cnt_l(p) the
+// entries of level l before position p, a tie run [s, e) holds c[l] = cnt_l(e) - cnt_l(s) cells of level l above
+// C[l] = cnt_l(s) of them; the thread at the run's tail adds, for the levels a that occur in it and every b > a,
+//   acc_u[a, b] += c[a] (2 C[b] + c[b])          (2 U_ab, a < b; U_ba = n_a n_b - U_ab at the end)
+//   acc_x[a, b] += c[a] c[b] (c[a] + c[b])       and f[a] += c[a]^3 - c[a]: sum (c[a] + c[b])^3 - (c[a] + c[b]) = f[a] + f[b] + 3 x[a, b]
+// in integer LDS atomics (exact: their order is immaterial); a run of RP_BIG entries or more is handed to the whole
+// workgroup instead, a slot per thread, behind a barrier (measured: one thread walking levels x levels for a run of 10 000
+// cells held its workgroup for longer than the sort took).  cnt_l(p) = at[wave of p][l] + pre[l][p]: the exclusive count
+// inside the wave from ballots (<= 63: a byte) on the absolute count at the wave's first entry; a run that began in an
+// earlier unit finds its start counts in open_at.  The run of the stored zeros is left out of the walk: with the implicit
+// zeros, nlev[l] - stored[l] per level, it is one group added at the end from the counts below it, and the groups above it
+// see the implicit zeros in their C.
+template <typename K>
+__global__ __launch_bounds__(RS_UNIT) void k_rs_pairs(const K* __restrict__ key, const uint16_t* __restrict__ lvl,
+                                                      const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,
+                                                      const unsigned int* __restrict__ kept, const int64_t* __restrict__ nlev,
+                                                      int n_bins, const int32_t* __restrict__ pairs, int n_pairs,
+                                                      long long* __restrict__ u2, double* __restrict__ tie) {
+  constexpr K K0 = (K)1 << (8 * sizeof(K) - 1);       // the key of +0.0
+  constexpr int WAVES = RS_UNIT / 64;
+  __shared__ unsigned long long acc_u[RP_SLOTS], acc_xlo[RP_SLOTS], f_lo[RP_MAX_LEVELS];
+  __shared__ unsigned int acc_xhi[RP_SLOTS], f_hi[RP_MAX_LEVELS];
+  __shared__ uint8_t pre[RP_MAX_LEVELS][RS_UNIT + 4];                 // column RS_UNIT stays 0: the end of the unit
+  __shared__ unsigned int at[WAVES + 1][RP_MAX_LEVELS], wtot[WAVES][RP_MAX_LEVELS];
+  __shared__ unsigned int open_at[RP_MAX_LEVELS], below[RP_MAX_LEVELS], upto[RP_MAX_LEVELS];   // upto: below and the stored zeros
+  __shared__ unsigned int zgrp[RP_MAX_LEVELS], above[RP_MAX_LEVELS], impl[RP_MAX_LEVELS];
+  __shared__ long long sh[RS_UNIT];
+  __shared__ unsigned int gc[RP_MAX_LEVELS], gC[RP_MAX_LEVELS];      // c and C of the long run in hand
+  __shared__ long long open_s;
+  __shared__ int has_below, has_upto, big_n, big_e[RP_BIG_MOST], big_s[RP_BIG_MOST];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int64_t g = g0 + blockIdx.x;
+  const long long k = (long long)kept[g];
+  key += seg[g] - base;
+  lvl += seg[g] - base;
+  for (int i = t; i < RP_SLOTS; i += RS_UNIT) {
+    acc_u[i] = 0;
+    acc_xlo[i] = 0;
+    acc_xhi[i] = 0;
+  }
+  if (t < RP_MAX_LEVELS) {
+    f_lo[t] = 0;
+    f_hi[t] = 0;
+    pre[t][RS_UNIT] = 0;
+    at[WAVES][t] = 0;
+    open_at[t] = below[t] = upto[t] = 0;
+  }
+  if (t == 0) has_below = has_upto = 0;
+  __syncthreads();
+  const auto cnt = [&](int p, int l) -> unsigned int { return at[p >> 6][l] + pre[l][p]; };   // p in [0, RS_UNIT]
+  long long carry = 0;
+  for (long long u0 = 0; u0 < k; u0 += RS_UNIT) {
+    const long long p = u0 + t;
+    const bool valid = p < k;
+    K kk = 0, before = 0;
+    bool head = false, tail = false;
+    unsigned int lv = RS_LEFT;
+    if (valid) {
+      kk = key[p];
+      lv = lvl[p];
+      if (p > 0) before = key[p - 1];
+      head = p == 0 || before != kk;
+      tail = p == k - 1 || key[p + 1] != kk;
+    }
+    const long long s = rs_scan_max(head ? p : (t == 0 ? carry : -1), sh, false);
+    carry = sh[RS_UNIT - 1];
+    // the counts of this unit
+    unsigned int mine = 0;
+    const unsigned long long lower = (1ull << lane) - 1ull;
+    for (int l = 0; l < n_bins; ++l) {
+      const unsigned long long mk = __ballot(lv == (unsigned int)l);
+      pre[l][t] = (uint8_t)__popcll(mk & lower);
+      if (lane == l) mine = (unsigned int)__popcll(mk);
+    }
+    if (lane < n_bins) wtot[wv][lane] = mine;
+    if (t == 0) big_n = 0;
+    __syncthreads();
+    if (t < n_bins) {
+      unsigned int run = at[WAVES][t];                // the end of the unit before
+      for (int w = 0; w < WAVES; ++w) {
+        at[w][t] = run;
+        run += wtot[w][t];
+      }
+      at[WAVES][t] = run;
+    }
+    __syncthreads();
+    const int pl = (int)(p - u0);
+    if (valid && kk >= K0 && (p == 0 || before < K0)) {               // the first entry that is not below zero
+      for (int l = 0; l < n_bins; ++l) below[l] = cnt(pl, l);
+      has_below = 1;
+    }
+    if (valid && kk > K0 && (p == 0 || before <= K0)) {               // the first entry above zero
+      for (int l = 0; l < n_bins; ++l) upto[l] = cnt(pl, l);
+      has_upto = 1;
+    }
+    if (valid && tail && kk != K0) {
+      const long long r = p + 1 - s;
+      if (r == 1) {                                                   // a run of one: c[a] = 1, nothing for the tie term
+        for (int b = (int)lv + 1; b < n_bins; ++b) {
+          const unsigned int Cb = cnt(pl, b);
+          if (Cb) atomicAdd(&acc_u[rp_slot((int)lv, b)], 2ull * Cb);
+        }
+      } else if (r >= RP_BIG) {                                       // for everybody, below
+        const int i = atomicAdd(&big_n, 1);
+        big_e[i] = pl + 1;
+        big_s[i] = s >= u0 ? (int)(s - u0) : -1;
+      } else {
+        const bool here = s >= u0;
+        const int sl = here ? (int)(s - u0) : 0;
+        unsigned long long present = 0;                               // the levels of its few entries, as a mask
+        for (long long j = s; j <= p; ++j) {
+          const unsigned int l = lvl[j];
+          if (l < (unsigned int)n_bins) present |= 1ull << l;         // (only a gene with a kept NaN can show RS_LEFT here)
+        }
+        for (unsigned long long todo = present; todo; todo &= todo - 1ull) {
+          const int a = __ffsll((long long)todo) - 1;
+          const unsigned long long ca = cnt(pl + 1, a) - (here ? cnt(sl, a) : open_at[a]);
+          rp_add128(&f_lo[a], &f_hi[a], rp_tie_term(ca));
+          for (int b = a + 1; b < n_bins; ++b) {
+            const unsigned int Cb = here ? cnt(sl, b) : open_at[b];
+            const unsigned long long cb = (present >> b & 1ull) ? cnt(pl + 1, b) - Cb : 0ull;
+            const unsigned long long add = ca * (2ull * Cb + cb);
+            if (add) atomicAdd(&acc_u[rp_slot(a, b)], add);
+            if (cb) rp_add128(&acc_xlo[rp_slot(a, b)], &acc_xhi[rp_slot(a, b)], u128_mul(ca * cb, ca + cb));
+          }
+        }
+      }
+    }
+    if (t == RS_UNIT - 1) open_s = valid && !tail && s >= u0 ? s : -1;   // a run that starts here and goes on
+    __syncthreads();
+    // the long runs that end in this unit, one after the other (in any order: the sums are integers), a slot per thread;
+    // nobody else adds meanwhile, so these are plain adds
+    for (int i = 0, nb = big_n; i < nb; ++i) {
+      if (t < n_bins) {
+        const unsigned int Cs = big_s[i] >= 0 ? cnt(big_s[i], t) : open_at[t];
+        gC[t] = Cs;
+        gc[t] = cnt(big_e[i], t) - Cs;
+      }
+      __syncthreads();
+      if (t < n_bins) {
+        const U128 f = u128_add({f_lo[t], (unsigned long long)f_hi[t]}, rp_tie_term(gc[t]));
+        f_lo[t] = f.lo;
+        f_hi[t] = (unsigned int)f.hi;
+      }
+      for (int j = t; j < RP_MAX_LEVELS * RP_MAX_LEVELS; j += RS_UNIT) {
+        const int a = j / RP_MAX_LEVELS, b = j % RP_MAX_LEVELS;
+        if (a >= b || b >= n_bins) continue;
+        const unsigned long long ca = gc[a], cb = gc[b];
+        if (!ca) continue;
+        const int q = rp_slot(a, b);
+        acc_u[q] += ca * (2ull * gC[b] + cb);
+        if (cb) {
+          const U128 x = u128_add({acc_xlo[q], (unsigned long long)acc_xhi[q]}, u128_mul(ca * cb, ca + cb));
+          acc_xlo[q] = x.lo;
+          acc_xhi[q] = (unsigned int)x.hi;
+        }
+      }
+      __syncthreads();
+    }
+    if (t < n_bins && open_s >= 0) open_at[t] = cnt((int)(open_s - u0), t);
+    __syncthreads();                                  // pre, at and sh are read before the next unit writes them
+  }
+  // the zero group and the shift of the groups above it
+  if (t < n_bins) {
+    const unsigned int st = at[WAVES][t];             // the stored entries of the level
+    const unsigned int up = has_upto ? upto[t] : st;
+    const unsigned int bl = has_below ? below[t] : up;
+    const long long im = (long long)nlev[t] - (long long)st;
+    below[t] = bl;
+    impl[t] = im > 0 ? (unsigned int)im : 0u;        // (only a gene with a kept NaN can show less)
+    zgrp[t] = up - bl + impl[t];
+    above[t] = st - up;
+    const U128 f = u128_add({f_lo[t], (unsigned long long)f_hi[t]}, rp_tie_term(zgrp[t]));
+    f_lo[t] = f.lo;
+    f_hi[t] = (unsigned int)f.hi;
+  }
+  __syncthreads();
+  for (int i = t; i < n_bins * n_bins; i += RS_UNIT) {
+    const int a = i / n_bins, b = i % n_bins;
+    if (a >= b) continue;
+    const int q = rp_slot(a, b);
+    const unsigned long long ca = zgrp[a], cb = zgrp[b];
+    acc_u[q] += ca * (2ull * below[b] + cb) + 2ull * above[a] * impl[b];
+    const U128 x = u128_add({acc_xlo[q], (unsigned long long)acc_xhi[q]}, u128_mul(ca * cb, ca + cb));
+    acc_xlo[q] = x.lo;
+    acc_xhi[q] = (unsigned int)x.hi;
+  }
+  __syncthreads();
+  for (int j = t; j < n_pairs; j += RS_UNIT) {
+    const int a = pairs[2 * j], b = pairs[2 * j + 1];
+    const int q = a < b ? rp_slot(a, b) : rp_slot(b, a);
+    const long long uab = (long long)acc_u[q];
+    u2[(int64_t)j * G + g] = a < b ? uab : 2ll * (long long)nlev[a] * (long long)nlev[b] - uab;
+    const U128 x = {acc_xlo[q], (unsigned long long)acc_xhi[q]};
+    const U128 tt = u128_add(u128_add({f_lo[a], (unsigned long long)f_hi[a]}, {f_lo[b], (unsigned long long)f_hi[b]}),
+                             u128_add(x, u128_add(x, x)));
+    tie[(int64_t)j * G + g] = (double)tt.hi * 18446744073709551616.0 + (double)tt.lo;
+  }
+}
+
 // a chunk table of the lists' shape for the dense form: gene g holds the entries [g n, (g + 1) n)
 int dense_table(cna_ctx* c, ExprState* s, RankSumWork* w, std::vector<int64_t>& seg_h, std::vector<int64_t>& gchunk_h) {
   const int64_t n = s->n, G = s->G, per = (n + RS_DENSE_CHUNK - 1) / RS_DENSE_CHUNK;
@@ -370,8 +604,10 @@ int dense_table(cna_ctx* c, ExprState* s, RankSumWork* w, std::vector<int64_t>& 
   return 0;
 }
 
-template <typename T>
-int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t work_bytes, int64_t m) {
+// Tiling, keys and the radix passes, shared by both entry points: for every tile of whole genes `behind(tile, base, keys,
+// levels, seg)` queues the kernel that reads the tile's sorted lists.  `who` names the entry in what is refused.
+template <typename T, class Behind>
+int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes, int64_t m, const char* who, Behind&& behind) {
   using K = typename KeyOf<T>::K;
   const int64_t n = s->n, G = s->G;
   const bool dense = s->format == 1;
@@ -410,7 +646,7 @@ int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t wo
     most_chunks = std::max(most_chunks, tiles.back().nch);
     most_genes = std::max(most_genes, g1 - g0);
   }
-  if (most_chunks > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_by: more than 2^31 - 1 chunks in one tile of genes");
+  if (most_chunks > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, std::string(who) + ": more than 2^31 - 1 chunks in one tile of genes");
   CNA_TRY(buf_need(c, s->st, w->keyA, (int64_t)sizeof(K) * most_entries));
   CNA_TRY(buf_need(c, s->st, w->keyB, (int64_t)sizeof(K) * most_entries));
   CNA_TRY(buf_need(c, s->st, w->lvlA, 2 * most_entries));
@@ -419,8 +655,6 @@ int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t wo
   CNA_TRY(buf_need(c, s->st, w->dbase, 4 * 256 * most_genes));
   CNA_TRY(buf_need(c, s->st, w->kept, 4 * G));
   CNA_TRY(buf_need(c, s->st, w->nanf, 4 * G));
-  CNA_TRY(buf_need(c, s->st, w->rank2, 8 * (int64_t)n_bins * G));
-  CNA_TRY(buf_need(c, s->st, w->tie, 8 * G));
   HIP_TRY(hipMemsetAsync(w->nanf.p, 0, (size_t)(4 * G), s->st));
   if (dense) {
     std::vector<unsigned int> all((size_t)G, (unsigned int)m);    // every kept cell is present in every gene
@@ -460,13 +694,39 @@ int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t wo
         std::swap(la, lb);
       }
     }
-    ProfScope ps(c, CNA_K_RANKSUM_RANK, s->st);
-    hipLaunchKernelGGL(k_rs_rank<K>, dim3(genes), dim3(RS_UNIT), 0, s->st, (const K*)ka, (const uint16_t*)la, seg, base, t.g0, G,
-                       w->kept.as<const unsigned int>(), w->sort.tot.as<const int64_t>(), m, n_bins, w->rank2.as<long long>(),
-                       w->tie.as<double>());
+    behind(t, base, (const K*)ka, (const uint16_t*)la, seg);
   }
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+template <typename T>
+int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t work_bytes, int64_t m) {
+  using K = typename KeyOf<T>::K;
+  const int64_t G = s->G;
+  CNA_TRY(buf_need(c, s->st, w->rank2, 8 * (int64_t)n_bins * G));
+  CNA_TRY(buf_need(c, s->st, w->tie, 8 * G));
+  return ranksum_sorted<T>(c, s, w, work_bytes, m, "cna_gene_ranksum_by",
+                           [&](const GeneTile& t, int64_t base, const K* key, const uint16_t* lvl, const int64_t* seg) {
+                             ProfScope ps(c, CNA_K_RANKSUM_RANK, s->st);
+                             hipLaunchKernelGGL(k_rs_rank<K>, dim3((unsigned)(t.g1 - t.g0)), dim3(RS_UNIT), 0, s->st, key, lvl, seg,
+                                                base, t.g0, G, w->kept.as<const unsigned int>(), w->sort.tot.as<const int64_t>(),
+                                                m, n_bins, w->rank2.as<long long>(), w->tie.as<double>());
+                           });
+}
+
+template <typename T>
+int pairs_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int n_pairs, int64_t work_bytes, int64_t m) {
+  using K = typename KeyOf<T>::K;
+  const int64_t G = s->G;
+  return ranksum_sorted<T>(c, s, w, work_bytes, m, "cna_gene_ranksum_pairs",
+                           [&](const GeneTile& t, int64_t base, const K* key, const uint16_t* lvl, const int64_t* seg) {
+                             ProfScope ps(c, CNA_K_RANKSUM_PAIRS, s->st);
+                             hipLaunchKernelGGL(k_rs_pairs<K>, dim3((unsigned)(t.g1 - t.g0)), dim3(RS_UNIT), 0, s->st, key, lvl, seg,
+                                                base, t.g0, G, w->kept.as<const unsigned int>(), w->sort.tot.as<const int64_t>(),
+                                                n_bins, w->pairs.as<const int32_t>(), n_pairs, w->u2.as<long long>(),
+                                                w->ptie.as<double>());
+                           });
 }
 
 }  // namespace
@@ -494,6 +754,50 @@ extern "C" int cna_gene_ranksum_by(cna_ctx* c, const int32_t* codes, int n_bins,
     CNA_TRY(fetch_results(s->st, "cna_gene_ranksum_by", {{rank2_out, w->rank2.p, (size_t)(8 * (int64_t)n_bins * G)},
                                                         {tie_out, w->tie.p, (size_t)(8 * G)},
                                                         {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
+  }
+  for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
+  for (int b = 0; b < n_bins; ++b) n_out[b] = w->sort.tot_h[(size_t)b];
+  return 0;
+}
+
+extern "C" int cna_gene_ranksum_pairs(cna_ctx* c, const int32_t* codes, int n_bins, const int32_t* pairs, int n_pairs,
+                                      int64_t work_bytes, int64_t* u2_out, double* tie_out, int64_t* n_out, uint8_t* nan_out) {
+  CHECK_CTX(c);
+  ExprState* s = expr_state(c);
+  if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_gene_ranksum_pairs: no expression matrix is resident (cna_expr_upload_*)");
+  if (!codes || !pairs || !u2_out || !tie_out || !n_out || !nan_out) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_pairs: null pointer");
+  if (n_bins < 1 || n_bins > RP_MAX_LEVELS) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_pairs: 1 <= n_bins <= 64");
+  if (n_pairs < 1 || n_pairs > RP_MAX_PAIRS) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_pairs: 1 <= n_pairs <= 2016");
+  if (work_bytes < 0) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_pairs: work_bytes is 0 (the default) or a number of bytes");
+  for (int j = 0; j < n_pairs; ++j) {
+    const int32_t a = pairs[2 * j], b = pairs[2 * j + 1];
+    if (a < 0 || a >= n_bins || b < 0 || b >= n_bins)
+      CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_pairs: a pair names a level outside [0, n_bins)");
+    if (a == b) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_pairs: a pair of one level with itself");
+  }
+  const int64_t G = s->G, out_count = (int64_t)n_pairs * G;
+  RankSumWork* w = expr_work<RankSumWork>(s, EXPR_RANKSUM);
+  // the codes are judged before anything is written; the sizes of the levels
+  CNA_TRY(sort_count(c, s->st, w->sort, CellList{}, codes, s->n, n_bins, 0, 2,
+                     "cna_gene_ranksum_pairs: a code lies outside [-1, n_bins)"));
+  int64_t m = 0;
+  for (int b = 0; b < n_bins; ++b) m += w->sort.tot_h[(size_t)b];
+  for (Buf* b : {&w->u2, &w->ptie}) {
+    const int rc = buf_need(c, s->st, *b, 8 * out_count);
+    if (rc == CNA_ENOMEM) (void)hipGetLastError();    // the refusal is the caller's to see, not the next launch's
+    CNA_TRY(rc);
+  }
+  CNA_TRY(buf_need(c, s->st, w->pairs, 8 * (int64_t)n_pairs));
+  // (ranksum_sorted waits for the stream before the caller has its list back)
+  HIP_TRY(hipMemcpyAsync(w->pairs.p, pairs, (size_t)(8 * n_pairs), hipMemcpyHostToDevice, s->st));
+  if (s->is_f64) CNA_TRY(pairs_run<double>(c, s, w, n_bins, n_pairs, work_bytes, m));
+  else CNA_TRY(pairs_run<float>(c, s, w, n_bins, n_pairs, work_bytes, m));
+  std::vector<unsigned int> nanf((size_t)G);
+  {
+    ProfScope ps(c, CNA_K_RANKSUM_FETCH, s->st);
+    CNA_TRY(fetch_results(s->st, "cna_gene_ranksum_pairs", {{u2_out, w->u2.p, (size_t)(8 * out_count)},
+                                                           {tie_out, w->ptie.p, (size_t)(8 * out_count)},
+                                                           {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
   }
   for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
   for (int b = 0; b < n_bins; ++b) n_out[b] = w->sort.tot_h[(size_t)b];

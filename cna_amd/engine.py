@@ -1346,6 +1346,28 @@ class Engine(_order.CellOrder):
                                            ptr(nan)), 'cna_gene_ranksum_by')
         return rank2, tie, n, nan.astype(bool)
 
+    def gene_ranksum_pairs(self, codes, n_levels, pairs, work_bytes=0):
+        """Level against level from one ranking of the kept cells of every gene (cna_gene_ranksum_pairs): `codes` int32
+        per cell, -1 = cell left out, at most 64 levels; `pairs` int32[P, 2] of (level, versus), at most 2016.  Returns
+        (u2 int64[P, genes]: twice the Mann-Whitney U of the level against the other one, tie float64[P, genes]: sum of
+        t^3 - t over the tie groups of the two levels' cells, n int64[n_levels]: cells per level, nan bool[genes]: a kept
+        cell of any level holds NaN and the gene's numbers mean nothing)."""
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        info = self.expression_shape()
+        if info['format'] != 'none' and codes.shape != (info['n_cells'],):
+            raise ValueError('gene_ranksum_pairs: %d codes for %d resident cells' % (codes.size, info['n_cells']))
+        if pairs.ndim != 2 or pairs.shape[1] != 2:
+            raise ValueError('gene_ranksum_pairs: pairs must be [P, 2], not %s' % (pairs.shape,))
+        n_levels, n_pairs = int(n_levels), int(pairs.shape[0])
+        u2 = np.empty((n_pairs, info['n_genes']), dtype=np.int64)
+        tie = np.empty((n_pairs, info['n_genes']))
+        n = np.empty(max(n_levels, 0), dtype=np.int64)
+        nan = np.empty(info['n_genes'], dtype=np.uint8)
+        check(self.lib.cna_gene_ranksum_pairs(self.h, ptr(codes), n_levels, ptr(pairs), n_pairs, int(work_bytes), ptr(u2),
+                                              ptr(tie), ptr(n), ptr(nan)), 'cna_gene_ranksum_pairs')
+        return u2, tie, n, nan.astype(bool)
+
     BW_KINDS = ('scott', 'silverman', 'constant')
 
     def coef_strata(self, v, fdr, codes, n_bins, fdr_thresh, points, bw_kind='scott', bw_value=0.0):

@@ -79,6 +79,9 @@ enum {
   /* cna_gene_ranksum_by on the expression stream: the keys and levels of a tile of genes; the passes of the radix sort;
    * the rank kernel; the copies of the results back (csrc/expr_ranksum.hip) */
   CNA_K_RANKSUM_KEYS, CNA_K_RANKSUM_SORT, CNA_K_RANKSUM_RANK, CNA_K_RANKSUM_FETCH,
+  /* cna_gene_ranksum_pairs: the kernel behind the sort (the keys, the sort and the copies back are counted under the ids
+   * above) */
+  CNA_K_RANKSUM_PAIRS,
   CNA_K_COUNT
 };
 
@@ -627,8 +630,8 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
                             int64_t n_genes, int64_t nnz, int index_bytes, int is_f64, int is_csc);
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
- * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster, cna_graph_components_find and
- * cna_gene_ranksum_by: cna_ctx_device_bytes returns to what it was before the upload. */
+ * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster, cna_graph_components_find,
+ * cna_gene_ranksum_by and cna_gene_ranksum_pairs: cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -748,6 +751,32 @@ int  cna_gene_corr_by(cna_ctx* ctx, const double* V, int q, const int32_t* codes
  * or a code outside [-1, n_bins) -- found on the device before anything else runs. */
 int  cna_gene_ranksum_by(cna_ctx* ctx, const int32_t* codes, int n_bins, int64_t work_bytes, int64_t* rank2_out,
                          double* tie_out, int64_t* n_out, uint8_t* nan_out);
+/* Level against level from the same ranking: what separates 'pos1' from 'neg1', or every population from one reference
+ * (scanpy's rank_genes_groups(reference=...)).  Order within the union of two levels is the order within all kept cells, so
+ * the one sort of cna_gene_ranksum_by gives every pair at once.  Walk the tie groups of a gene in ascending order; with
+ * c[l] the kept cells of level l in a group and C[l] those strictly below it,
+ *   u2_out[k * n_genes + g]  = sum over the groups of c[a] (2 C[b] + c[b]) = 2 U_ab for pair k = (a, b) = (pairs[2k],
+ *   pairs[2k + 1]): twice scipy.stats.mannwhitneyu(x_a, x_b).statistic, an integer; 0 when either level is empty;
+ *   u2_ab + u2_ba = 2 n_a n_b
+ *   tie_out[k * n_genes + g] = sum over the groups of t^3 - t, t = c[a] + c[b]: the tie term over a u b.  Accumulated in
+ *   integers (96 bits per accumulator: enough for 2^31 cells) and rounded to double once at the end: exact whenever
+ *   below 2^53, the same bits on every run and for a CSR and a CSC upload of one matrix
+ *   n_out[b], nan_out[g]     as in cna_gene_ranksum_by (a NaN in a kept cell of ANY level flags the gene for every pair)
+ * codes, work_bytes, the value semantics (-0.0 = +0.0 = a stored zero = the implicit zeros, +-inf ordinary, float64 on 64
+ * bits), the keys and the sort are those of cna_gene_ranksum_by; the kept cells are those with a code >= 0.
+ *   1 <= n_bins <= 64 levels take part; 1 <= n_pairs <= 2016; every pair has a != b, both in [0, n_bins); a pair may repeat
+ *   and (b, a) may stand beside (a, b).
+ * Behind the sort one workgroup per gene walks the sorted list forward once, per-level prefix counts from wave ballots and
+ * one integer accumulator per unordered pair of levels in LDS; the implicit zeros of the gene-major form join the stored
+ * zeros' group by arithmetic.  Runs on the expression stream with the work buffers of cna_gene_ranksum_by (grow-only, freed
+ * by cna_expr_drop), changes no other state, works on a context that never saw a graph and may be called between
+ * cna_null_local_launch and cna_null_local_fetch.
+ * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL, with nothing written: a null pointer, n_bins, n_pairs or
+ * work_bytes out of range, a pair with a == b or a level outside [0, n_bins) (checked on the host), or a code outside
+ * [-1, n_bins) -- found on the device before anything else runs.  CNA_ENOMEM: the two n_pairs x n_genes result buffers do
+ * not fit; the context stays usable. */
+int  cna_gene_ranksum_pairs(cna_ctx* ctx, const int32_t* codes, int n_bins, const int32_t* pairs, int n_pairs,
+                            int64_t work_bytes, int64_t* u2_out, double* tie_out, int64_t* n_out, uint8_t* nan_out);
 
 /* ---- the expression matrix against the working matrix (csrc/expr_cross.hip) ------------------- */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
