@@ -21,7 +21,7 @@ int cna_assoc_begin(cna_ctx* c, int nsteps, const double* y_hint, int n_hint) {
   if (!c) CNA_FAIL(CNA_EINVAL, "null context");
   if (nsteps < 0) CNA_FAIL(CNA_EINVAL, "cna_assoc_begin: nsteps < 0");
   if (nsteps == 0) return 0;                       // the NAM of the resident walk stays (the caller's NAM cache)
-  // the hint is consumed by the step that ends a walk of two or more steps (c_api.hip:cna_nam_step); never leave one behind
+  // the hint is consumed by the step that ends a walk of two or more steps (walk.hip:cna_nam_step); never leave one behind
   if (y_hint && nsteps >= 2) CNA_TRY(cna_nam_select_hint(c, y_hint, n_hint));
   return cna_nam_steps(c, nsteps);
 }

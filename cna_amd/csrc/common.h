@@ -79,8 +79,8 @@ struct NullPass {
   std::atomic<int64_t> status_off{-1};       // >= 0: h_res + off holds the pending integer pass's status word (0: its sums stand)
 };
 struct CellColumns {
-  std::atomic<bool> coef_early{false};        // [void_x] h_cell[0, n_out) already holds the coefficients of the current ncorrs
-  std::atomic<bool> fdr_inline{false};        // [void_x] ... and the FDR column follows the last local-null pass on the device
+  std::atomic<bool> coef_early{false};        // [void_coef] h_cell[0, n_out) already holds the coefficients of the current ncorrs
+  std::atomic<bool> fdr_inline{false};        // [void_coef] ... and the FDR column follows the last local-null pass on the device
   std::atomic<bool> fdr_early_copied{false};  // cna_percell_fdr_copy_early took the FDR column of the pending pass ...
   std::atomic<bool> fdr_early_served{false};  // ... and cna_percell_fdr_pinned then returned that same column
   std::atomic<int> fdr_early_inflight{0};     // a helper thread is inside cna_percell_fdr_copy_early
@@ -98,8 +98,9 @@ struct CellColumns {
 };
 
 // Derived state: each flag (here and in CellColumns) that says "still holds" is tagged with the transition of c_api.hip that clears it --
-// [void_x] X and what is derived from it, [void_walk] the walk and then X, [void_cells] the cell space and then the walk.
-// A new such flag goes into the transition of what it is derived from.
+// [void_coef] the per-cell columns copied from the coefficients, [void_x] those, X and what is derived from it, [void_walk] the walk
+// and then X, [void_cells] the cell space and then the walk; beside them [void_x_nam_link], what ties X to the NAM that a walk
+// step is about to replace.  A new such flag goes into the transition of what it is derived from.
 struct cna_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -220,7 +221,7 @@ struct cna_ctx {
   bool x_valid = false, x_from_nam = false;   // [void_x]
   int64_t x_gen = 0;               // [void_x] counts the times X was voided (cna_x_generation): a caller's memo of something
                                    //   derived from X (engine.expr_cross) holds while this stands still
-  bool x_ident = false;            // [void_x] X = standardised NAM, every cell, samples in place, nothing regressed out (cna_x_identity)
+  bool x_ident = false;            // [void_x, void_x_nam_link] X = standardised NAM, every cell, samples in place, nothing regressed out (cna_x_identity)
   // The selection pass as a by-product of the walk's last step (cna_nam_select_hint): when the caller says which
   // standardised phenotype the analysis will use and nothing will be filtered or regressed out, the last step's
   // write-out also leaves X = centred / standardised NAM, its digit planes, the coefficients X.y/N and the
@@ -228,10 +229,10 @@ struct cna_ctx {
   // it has just written -- and that call then finds its work done (the 1.5 ms pass at 2M x 200 leaves the path).
   std::vector<double> byp_hint;    // y of a pending hint (consumed by the next last step)
   std::vector<double> byp_y;       // y the by-product on the device was made for
-  bool byp_valid = false;          // [void_x] X / planes / coefficients on the device are that by-product
+  bool byp_valid = false;          // [void_x, void_x_nam_link] X / planes / coefficients on the device are that by-product
   bool byp_with_q = false;
   bool byp_skip_nam = false;       // ... and it does not write the NAM (nam_lazy afterwards)
-  bool nam_lazy = false;           // [void_walk] the NAM is one more run of the last step away (c_api.hip:need_nam)
+  bool nam_lazy = false;           // [void_walk, void_x_nam_link] the NAM is one more run of the last step away (walk.hip:need_nam)
   int lazy_steps_before = 0;       // steps_done when that step was launched
   bool byp_arm = false;            // the launch being issued is that last step (launch_nam_step reads it)
   void* pair_buf = nullptr;        // {count, max bits} of every rank: the selection pass's two counters in one collective
@@ -298,7 +299,7 @@ struct cna_ctx {
   hipStream_t gram_stream = nullptr;
   int gram_stream_state = 0;             // 0: not created yet, 1: ready, -1: unavailable
   hipEvent_t gram_pre_done = nullptr, range_done = nullptr;
-  bool gram_pre = false;                 // [void_x]
+  bool gram_pre = false;                 // [void_x, void_x_nam_link]
   bool gram_pre_pending = false;         // kernels of a ranged product may still run on gram_stream (nobody has waited for gram_pre_done yet)
   void* gram_part = nullptr;
   int64_t gram_part_cap = 0;
@@ -376,7 +377,39 @@ inline int64_t carve_bytes(std::initializer_list<int64_t> sizes) {
   return t;
 }
 
-int x_ld(int Nx);   // c_api.hip: leading dimension of a working matrix with Nx samples
+// ---- c_api.hip: the transitions that void derived state, and the bracket every producer of X puts around its work
+void void_coef(cna_ctx* c);         // the per-cell columns copied from the coefficients
+void void_x(cna_ctx* c);            // those, X and everything derived from it
+void void_walk(cna_ctx* c);         // the walk (state, NAM), then X
+void void_cells(cna_ctx* c);        // the cell space the first step reads, then the walk
+void void_x_nam_link(cna_ctx* c);   // what ties X to the NAM that a walk step is about to replace
+int x_begin(cna_ctx* c, const char* who);                                                       // in place: the shape stays
+int x_begin(cna_ctx* c, const char* who, int64_t nx, int Nx, const int64_t* keep_idx);          // a new shape
+void x_commit(cna_ctx* c, bool from_nam, bool ncorrs, bool xq, bool ident);
+int x_ld(int Nx);   // leading dimension of a working matrix with Nx samples
+
+// ---- walk.hip
+// entry points that read or replace the NAM collect a pending walk's verdict first
+#define AUTO_FINISH(c)                                                   \
+  do {                                                                   \
+    if ((c)->auto_pending) CNA_TRY(cna_nam_auto_finish((c), nullptr, nullptr)); \
+  } while (0)
+int exchange_stat(cna_ctx* c);                                      // c->stat (NAM space): every rank's block to every rank
+int need_nam(cna_ctx* c);                                           // the NAM on the device, for whoever reads it
+int ensure_auto_state(cna_ctx* c, unsigned long long** hist);       // the medians' bookkeeping block and its histogram words
+
+// ---- xprod.hip
+int reserve_ncorrs(cna_ctx* c, int64_t rows);                       // c->ncorrs for that many rows of X
+
+// ---- gram_host.hip: the host side of the Gram matrix, for the passes that queue it themselves
+int gram_overlap_ranges();
+int ensure_gram_stream(cna_ctx* c);
+int gram_host_reserve(cna_ctx* c, int Nx);
+bool gram_solo(cna_ctx* c);
+int gram_host_finish(cna_ctx* c, int Nx);
+int gram_pre_settle(cna_ctx* c);
+int gram_launch_now(cna_ctx* c);                                    // cna_gram_launch behind its checks
+
 // local_null.hip: the two halves of a pass (cna_select_standardized_fused issues them itself)
 int null_local_prepare(cna_ctx* c, int P, const double* edges, int T, int want_tails, const double* thr);
 int null_local_go(cna_ctx* c, int col0);
@@ -386,10 +419,11 @@ void expr_destroy(cna_ctx* c);
 
 // ---- collectives (comm.hip)
 inline bool comm_active(const cna_ctx* c) { return c->comm != nullptr || c->shm != nullptr; }
+int comm_destroy(cna_ctx* c);
 int comm_halo_exchange(cna_ctx* c, const double* sendbuf, double* recvbuf, int64_t doubles_per_row, hipStream_t st = nullptr);
 // column indices of the local graph block -> rows of the compact state (cna_ctx::t_compact): own rows 0 .. n_local - 1, the
 // rows of the ascending receive list behind them; *bad = 1 when an index is neither (diffuse.hip)
-// the main stream waits for an exchange still in flight on the halo stream (c_api.hip); no-op when none is
+// the main stream waits for an exchange still in flight on the halo stream (walk.hip); no-op when none is
 int halo_settle(cna_ctx* c);
 // flags[row] = 1 when the row's graph block references a column outside [row0, row0 + n_local) (diffuse.hip)
 int launch_rows_need_halo(cna_ctx* c, unsigned char* flags_dev);

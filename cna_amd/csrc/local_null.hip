@@ -441,8 +441,7 @@ static int ensure_cell_pinned(cna_ctx* c, int64_t n_out) {
   if (need > c->cells.h_cell_cap) {
     if (c->cells.h_cell) HIP_TRY(hipHostFree(c->cells.h_cell));
     c->cells.h_cell = nullptr;
-    c->cells.coef_early = false;
-    c->cells.fdr_inline = false;
+    void_coef(c);                   // (the pinned block that held the columns is gone)
     HIP_TRY(hipHostMalloc(&c->cells.h_cell, (size_t)need, hipHostMallocDefault));
     c->cells.h_cell_cap = need;
   }

@@ -1,7 +1,7 @@
 """Inputs for the exact order statistics on the device (plain numpy, importable without a GPU).
 
 Three places in csrc select a median by an eight-pass radix select over the order-preserving 64-bit key of a double:
-rows.hip (k_digit_hist2 + k_auto_pick: the walk's stop rule, cna_stat_median, cna_stat_qc), c_api.hip (stat_select over
+rows.hip (k_digit_hist2 + k_auto_pick: the walk's stop rule, cna_stat_median, cna_stat_qc), walk.hip (stat_select over
 k_digit_hist, CNA_MEDIAN_HOST=1) and strata.hip (k_st_hist + k_st_pick, every bin of cna_coef_strata at once).  Such a
 select is right or wrong by bit pattern, so the vectors here are built from integer keys: which digit pass parts the two
 middle elements, which digit the middle element has at a pass, and so on, hold exactly and are asserted on the keys

@@ -403,6 +403,24 @@ def test_coefficients_do_not_outlive_the_walk(eng, small, what):
     assert not eng.x_identity_resident()
 
 
+def test_early_coefficient_column_does_not_outlive_its_coefficients(eng, small):
+    """select_standardized with y, the early coefficient column launched and collected, then cna_ncorrs with another
+    phenotype on the same X: the pinned column holds the coefficients of the old y, and cna_percell_coef_wait refuses
+    (CNA_ESTATE) instead of serving it (csrc/c_api.hip: void_coef)."""
+    from cna_amd import _ffi
+    data, other, y = small
+    eng.null_local_discard()
+    _walk(eng, data, NS)
+    nz, _ = eng.select_standardized(None, None, y=y)
+    assert nz == 0
+    assert eng.percell_coef_launch()
+    eng.percell_coef_wait()
+    y2 = np.random.RandomState(11).randn(NS)
+    eng.ncorrs((y2 - y2.mean()) / y2.std())
+    with pytest.raises(_ffi.CnaHipError, match=r'status -4\)'):
+        eng.percell_coef_wait()
+
+
 NW, PW = 96, 256          # more than 64 samples: the walk's last step can leave the selection by-product (t_ld > 64)
 
 

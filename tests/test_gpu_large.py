@@ -80,7 +80,7 @@ def _check_full_result(res, data, y, N, Nnull, covs=None):
     X = res.namresid.values
     if covs is None:
         # Under the default schedule X is the by-product of the walk's last step (diffuse.hip:select_tail) and the raw
-        # NAM comes from a SECOND run of that step (c_api.hip:need_nam): the two must be the same matrix -- X is the
+        # NAM comes from a SECOND run of that step (walk.hip:need_nam): the two must be the same matrix -- X is the
         # NAM centred and divided by its std per cell (_nam.py:122,159), entry by entry, at full size
         for c0 in range(0, n, 250_000):
             blk = nam[:, c0:c0 + 250_000]

@@ -260,7 +260,7 @@ def test_compressed_second_step_across_ranks(world, defer, monkeypatch):
 @pytest.mark.parametrize('world', [2, 4])
 def test_state_for_local_and_halo_rows_only(world, monkeypatch):
     """a rank owns its rows of the graph AND of the state.  With the halo exchange the diffusion state holds
-    this rank's rows followed by the rows it receives (csrc/c_api.hip:cna_set_halo, `t_compact`), the walk reads the graph
+    this rank's rows followed by the rows it receives (csrc/walk.hip:cna_set_halo, `t_compact`), the walk reads the graph
     through column indices renumbered into that row space, and what arrives lands in the tail directly.  Same bits as the
     global row space (CNA_COMPACT_STATE=0) and as one GPU; and the device memory of a rank shrinks with the block."""
     import multiprocessing as mp

@@ -2,7 +2,7 @@
 MI355X; the inputs and what they are made for: tests/order_stats.py, checked in tests/test_order_stats_host.py).
 
   rows.hip    k_digit_hist2 + k_auto_pick (launch_auto_median): cna_stat_median, cna_stat_qc, the walk's stop rule
-  c_api.hip   stat_select over k_digit_hist: cna_stat_median under CNA_MEDIAN_HOST=1
+  walk.hip    stat_select over k_digit_hist: cna_stat_median under CNA_MEDIAN_HOST=1
   rows.hip    k_qc_count: the cells failing `kurtosis < max(6, 2 median)`
   strata.hip  k_st_hist + k_st_pick: the median column of cna_coef_strata, every bin at once
 

@@ -1066,7 +1066,7 @@ def test_selection_as_a_by_product_of_the_last_walk_step(eng, monkeypatch, n, N,
 def test_gram_under_the_walks_last_step(eng, monkeypatch, n, N, K, nsteps):
     """NAM.dot(NAM.T) (_nam.py:105) is a sum over cells, and the walk's last step writes the standardised rows one by one
     (select_tail): that step runs in K row ranges and the Gram kernel of each range follows it on a second stream, carrying
-    its partial tiles from range to range (c_api.hip:ranged_last_step, mfma.hip:launch_gram_range).  Every workgroup adds
+    its partial tiles from range to range (walk.hip:ranged_last_step, mfma.hip:launch_gram_range).  Every workgroup adds
     the same slabs in the same order as the one-launch kernel, so the matrix -- and with it every result -- is the same
     bit for bit.  The 3 x 3-block kernel on 16 waves (200 / 180 samples) and on 8 (100), the tile-per-wave kernel with two
     slabs in LDS (80: k_gram_db; the step is split only beyond 64 samples) and with one (300: k_gram, two grid.y passes),
@@ -1337,7 +1337,7 @@ def test_nam_cache_on_device(eng):
 
 def test_nam_cache_after_a_walk_that_left_the_selection_instead_of_the_nam(monkeypatch):
     """The schedule of large inputs: the walk's last step does the selection pass and does not write the raw NAM
-    (cna_nam_select_hint).  res.nam of that call is one more run of the last step (c_api.hip:need_nam).  A second
+    (cna_nam_select_hint).  res.nam of that call is one more run of the last step (walk.hip:need_nam).  A second
     phenotype on the same dataset skips the walk (NAM cache) AND the selection pass -- the standardised NAM does not depend
     on the phenotype and is still on the device (cna_x_identity): only its coefficients are taken -- and gives what a
     from-scratch run gives (the NAM bit for bit)."""
