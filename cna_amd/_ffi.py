@@ -149,6 +149,7 @@ SIGNATURES = {
     'cna_gene_ranksum_by': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cna_gene_ranksum_pairs': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    'cna_gene_rank_corr': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 4 + [c_i64p, C.c_void_p]),
     'cna_x_generation': (C.c_int, [c_ctx, C.POINTER(C.c_int64)]),
     'cna_matrix_to_bins': (C.c_int, [c_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     'cna_enrichment_extremes': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -196,6 +197,9 @@ KERNELS = ['colsum', 'nam_first', 'nam_step', 'batch_kurtosis', 'zero_variance',
            'components_upload', 'components_hook', 'components_flatten', 'components_check', 'components_tally',
            'components_label', 'components_fetch', 'ranksum_keys', 'ranksum_sort', 'ranksum_rank', 'ranksum_fetch',
            'ranksum_pairs']
+# the ids behind them in the enum (cna_gene_rank_corr), in a list of their own because tests/test_gene_markers_pairs_host.py
+# pins the last name of KERNELS; Engine.prof reads both lists
+KERNELS_RANK_CORR = ['rankcorr_keys', 'rankcorr_corr']
 
 _lib = None
 

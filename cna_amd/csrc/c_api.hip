@@ -104,7 +104,7 @@ static const char* kKernelNames[CNA_K_COUNT] = {
     "raster_upload", "raster", "raster_fetch",
     "components_upload", "components_hook", "components_flatten", "components_check", "components_tally", "components_label",
     "components_fetch", "ranksum_keys", "ranksum_sort", "ranksum_rank", "ranksum_fetch",
-    "ranksum_pairs"};
+    "ranksum_pairs", "rankcorr_keys", "rankcorr_corr"};
 
 // Derived state holds only as long as what it was derived from.  Four nested transitions, and void_x_nam_link beside them,
 // are the only places that clear it (common.h tags every flag with the innermost transition that clears it); they assign

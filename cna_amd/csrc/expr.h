@@ -5,8 +5,9 @@
 // this stream and these buffers), cna_expr_cross_by (expr_cross_by.hip), cna_gram_by (gram_by.hip: X alone) and
 // cna_coef_raster (raster.hip: no matrix, this stream, the sort twice); cna_graph_components_* (components.hip) borrows the
 // stream and a slot of buffers and reads the resident graph; cna_gene_ranksum_by (expr_ranksum.hip: a ranking of the cells
-// of every gene, with a radix sort of its own on the chunk tables) and cna_gene_ranksum_pairs (the same file, sort and
-// buffers: level against level).  What two of them need is here once:
+// of every gene, with a radix sort of its own on the chunk tables), cna_gene_ranksum_pairs (the same file, sort and
+// buffers: level against level) and cna_gene_rank_corr (the same again: the sort with the cell as payload, Spearman's rho
+// against per-cell columns).  What two of them need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared
 //   ExprState       the resident matrix, the stream, and one slot of work buffers per entry point
 //   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins and cna_gene_corr_by, value

@@ -30,7 +30,23 @@
 //                         ballots, so that every tie run knows its cells per level and those below it; 2 U and the tie term
 //                         of every unordered pair of at most 64 levels in integer accumulators in LDS (stated at the kernel)
 //
-// The genes go in tiles of whole genes whose keys, levels and their ping-pong copies stay within work_bytes (0:
+// cna_gene_rank_corr: Spearman's rank correlation of every gene with up to 16 per-cell columns (cna.tl.gene_rank_corr), as
+// exact integers.  The payload of the sort is a template parameter: the level of the entry's cell (uint16_t, the two entries
+// above, bit for bit what they were) or the cell itself (uint32_t); rs_passes is the part of the sort that knows a chunk
+// table and nothing of the resident matrix, so the columns are ranked by the same passes.
+//   k_rc_mask             the kept cells (every column finite) as the codes ranksum_sorted expects, and their number m
+//   k_rc_vkeys            the columns as q segments of n entries {float64 key, cell} in a table of the dense form's shape
+//   k_rc_keyrank          behind their sort, one thread per kept entry: its tie run [s, e), by binary search where a neighbour
+//                         ties -> b = s + e - m (twice the midrank less m + 1) into the cell-major table btab[cell][W]; the
+//                         column's tie term in integers
+//   k_rc_corr             behind the genes' sort, one workgroup per gene: a = s + e - m of every entry by the forward and
+//                         backward walks of k_rs_rank, the cell's row of btab gathered in each, sum a b per column in 96-bit
+//                         integer registers, the implicit zeros by arithmetic; the two limbs of S and the gene's tie term
+// (forward / backward and not the single forward walk of k_rs_pairs: a = (s - m) + e is linear, so each walk adds its own
+// half with the coefficient it has in hand and nothing about an open run is carried from unit to unit but its start; the
+// price is the second gather of the row, which comes from the same table in reverse order)
+//
+// The genes go in tiles of whole genes whose keys, payloads and their ping-pong copies stay within work_bytes (0:
 // RS_WORK_BYTES); a gene that alone exceeds it is one tile.  The counters of the sort (1 KB per chunk) come on top.
 #include "expr.h"
 
@@ -41,7 +57,8 @@ constexpr int64_t RS_WORK_BYTES = 1ll << 30;   // keys + levels + their copies o
 constexpr int64_t RS_DENSE_CHUNK = 1024;       // cells of one gene per sort chunk of the dense form (build_chunks' least)
 constexpr int RS_UNIT = 256;                   // entries of a gene's sorted list the rank kernel takes at a time
 constexpr int RS_TILE = 64;                    // the dense gather's square tile
-constexpr uint16_t RS_LEFT = 0xffff;           // "level" of an entry whose cell is left out
+constexpr uint16_t RS_LEFT = 0xffff;           // "level" of an entry whose cell is left out (rs_left<uint16_t>())
+constexpr int RC_MAX_KEYS = 16;                // cna_gene_rank_corr: per-cell columns of one call
 constexpr int RP_MAX_LEVELS = 64;              // cna_gene_ranksum_pairs: levels that take part,
 constexpr int RP_SLOTS = 2016;                 // their unordered pairs (the accumulators in LDS) and
 constexpr int RP_MAX_PAIRS = 2016;             // the pairs of one call
@@ -56,6 +73,26 @@ struct RankSumWork : BufSet {
       tie{*this};
   Buf pairs{*this}, u2{*this}, ptie{*this};                            // cna_gene_ranksum_pairs: its pairs and results
   Buf seg{*this}, chunk_lo{*this}, chunk_gene{*this}, gchunk{*this};   // the dense form's table (the lists have the state's)
+  // cna_gene_rank_corr: the columns, the kept cells' count, b[cell][W], the columns' tie terms (96 bits), the two limbs of S
+  Buf vcol{*this}, vm{*this}, btab{*this}, tiek{*this}, slo{*this}, shi{*this};
+};
+
+// What an entry carries through the sort beside its key: the level of its cell (uint16_t: the rank sums) or the cell
+// itself (uint32_t: cna_gene_rank_corr).  All ones: the cell is left out.
+template <typename P>
+constexpr P rs_left() { return (P) ~(P)0; }
+template <typename P>
+__device__ __forceinline__ P rs_payload(int64_t cell, int32_t code) {
+  if constexpr (sizeof(P) == 2) return (P)code;
+  else return (P)cell;
+}
+static_assert(rs_left<uint16_t>() == RS_LEFT, "the rank and pairs kernels compare with RS_LEFT");
+
+// a chunk table on the device: segment g holds the entries [seg[g], seg[g + 1]) in the chunks [gchunk[g], gchunk[g + 1])
+struct SortTable {
+  const int64_t *seg, *chunk_lo, *gchunk;
+  const int32_t* chunk_gene;
+  int64_t chunk_len;
 };
 
 // ------------------------------------------------------------------ keys
@@ -84,12 +121,12 @@ __device__ __forceinline__ typename KeyOf<T>::K rs_key(T x, bool* is_nan) {
 }
 
 // workgroup = chunk c0 + blockIdx.x of the gene lists; tile arrays are indexed by entry - base
-template <typename T>
+template <typename T, typename P>
 __global__ __launch_bounds__(256) void k_rs_keys_sparse(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
                                                         const int64_t* __restrict__ gptr, int64_t c0, int64_t chunk_len,
                                                         const int32_t* __restrict__ gcell, const T* __restrict__ gval,
                                                         const int32_t* __restrict__ codes, int64_t base,
-                                                        typename KeyOf<T>::K* __restrict__ key, uint16_t* __restrict__ lvl,
+                                                        typename KeyOf<T>::K* __restrict__ key, P* __restrict__ lvl,
                                                         unsigned int* __restrict__ kept, unsigned int* __restrict__ nanf) {
   using K = typename KeyOf<T>::K;
   const int64_t ch = c0 + blockIdx.x;
@@ -99,13 +136,13 @@ __global__ __launch_bounds__(256) void k_rs_keys_sparse(const int64_t* __restric
   unsigned int mine = 0;
   bool seen_nan = false;
   for (int64_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
-    const int32_t cd = codes[gcell[e]];
+    const int32_t cell = gcell[e], cd = codes[cell];
     K k = ~(K)0;
-    uint16_t l = RS_LEFT;
+    P l = rs_left<P>();
     if (cd >= 0) {
       bool is_nan;
       k = rs_key<T>(gval[e], &is_nan);
-      l = (uint16_t)cd;
+      l = rs_payload<P>(cell, cd);
       seen_nan = seen_nan || is_nan;
       ++mine;
     }
@@ -122,26 +159,26 @@ __global__ __launch_bounds__(256) void k_rs_keys_sparse(const int64_t* __restric
 }
 
 // workgroup = RS_TILE cells x RS_TILE genes of the tile [g0, g1): X[cell][gene] in, entry (gene * n + cell) - base out
-template <typename T>
+template <typename T, typename P>
 __global__ __launch_bounds__(256) void k_rs_keys_dense(const T* __restrict__ X, int64_t n, int64_t G, int64_t g0, int64_t g1,
                                                        const int32_t* __restrict__ codes, int64_t base,
-                                                       typename KeyOf<T>::K* __restrict__ key, uint16_t* __restrict__ lvl,
+                                                       typename KeyOf<T>::K* __restrict__ key, P* __restrict__ lvl,
                                                        unsigned int* __restrict__ nanf) {
   using K = typename KeyOf<T>::K;
   __shared__ K tk[RS_TILE][RS_TILE + 1];
-  __shared__ uint16_t tl[RS_TILE];
+  __shared__ P tl[RS_TILE];
   const int tx = threadIdx.x % RS_TILE, ty = threadIdx.x / RS_TILE;
   const int64_t cell0 = (int64_t)blockIdx.x * RS_TILE, gene0 = g0 + (int64_t)blockIdx.y * RS_TILE;
   if (threadIdx.x < RS_TILE) {
     const int64_t i = cell0 + threadIdx.x;
     const int32_t cd = i < n ? codes[i] : -1;
-    tl[threadIdx.x] = cd >= 0 ? (uint16_t)cd : RS_LEFT;
+    tl[threadIdx.x] = cd >= 0 ? rs_payload<P>(i, cd) : rs_left<P>();
   }
   __syncthreads();
   for (int r = ty; r < RS_TILE; r += 256 / RS_TILE) {
     const int64_t i = cell0 + r, g = gene0 + tx;
     K k = ~(K)0;
-    if (i < n && g < g1 && tl[r] != RS_LEFT) {
+    if (i < n && g < g1 && tl[r] != rs_left<P>()) {
       bool is_nan;
       k = rs_key<T>(X[i * G + g], &is_nan);
       if (is_nan) nanf[g] = 1u;
@@ -203,11 +240,11 @@ __global__ __launch_bounds__(256) void k_rs_scan(const int64_t* __restrict__ gch
 
 // one wave per chunk; cur[digit] = where the chunk's next entry with that digit goes inside the gene's segment.  In a batch
 // of 64 entries the lanes with one digit find each other with 8 ballots and take consecutive places in lane order.
-template <typename K>
+template <typename K, typename P>
 __global__ __launch_bounds__(64) void k_rs_scatter(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
                                                    const int64_t* __restrict__ seg, int64_t c0, int64_t chunk_len, int64_t base,
-                                                   int64_t g0, const K* __restrict__ kin, const uint16_t* __restrict__ lin,
-                                                   K* __restrict__ kout, uint16_t* __restrict__ lout, int shift,
+                                                   int64_t g0, const K* __restrict__ kin, const P* __restrict__ lin,
+                                                   K* __restrict__ kout, P* __restrict__ lout, int shift,
                                                    const unsigned int* __restrict__ cnt, const unsigned int* __restrict__ dbase) {
   __shared__ unsigned int cur[256];
   const int lane = threadIdx.x;
@@ -221,7 +258,7 @@ __global__ __launch_bounds__(64) void k_rs_scatter(const int64_t* __restrict__ c
     const int64_t e = e0 + lane;
     const bool valid = e < hi;
     K k = 0;
-    uint16_t l = 0;
+    P l = 0;
     if (valid) {
       k = kin[e - base];
       l = lin[e - base];
@@ -576,65 +613,317 @@ __global__ __launch_bounds__(RS_UNIT) void k_rs_pairs(const K* __restrict__ key,
   }
 }
 
-// a chunk table of the lists' shape for the dense form: gene g holds the entries [g n, (g + 1) n)
-int dense_table(cna_ctx* c, ExprState* s, RankSumWork* w, std::vector<int64_t>& seg_h, std::vector<int64_t>& gchunk_h) {
-  const int64_t n = s->n, G = s->G, per = (n + RS_DENSE_CHUNK - 1) / RS_DENSE_CHUNK;
-  std::vector<int64_t> lo((size_t)(G * per));
-  std::vector<int32_t> gene((size_t)(G * per));
-  seg_h.resize((size_t)G + 1);
-  gchunk_h.resize((size_t)G + 1);
-  for (int64_t g = 0; g <= G; ++g) {
-    seg_h[(size_t)g] = g * n;
+// ------------------------------------------------------------------ rank correlation (cna_gene_rank_corr)
+// With r the midrank over the m kept cells, a_i = 2 r_gene(i) - (m + 1) and b_i = 2 r_column(i) - (m + 1) are integers
+// that sum to 0 over the kept cells, and a tie run [s, e) of a sorted list gives each of its entries s + e - m.
+//   S[k, g] = sum over the kept cells of a_i b_i[k]      rho = 3 S / sqrt((m^3 - m - T_g) (m^3 - m - T_k))   (the host's line)
+// |S| <= (m^3 - m) / 3 passes 2^63 from 3 024 617 cells on, so S is summed and returned in 128 bits.
+
+// codes[i] = 0 where every column is finite, else -1; *m += their number
+__global__ __launch_bounds__(256) void k_rc_mask(const double* __restrict__ V, int q, int64_t n, int32_t* __restrict__ codes,
+                                                 unsigned long long* __restrict__ m) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool keep = i < n;
+  if (i < n) {
+    for (int k = 0; k < q; ++k) keep = keep && finite_d(V[(int64_t)k * n + i]);
+    codes[i] = keep ? 0 : -1;
+  }
+  const unsigned long long bal = __ballot(keep);
+  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(m, (unsigned long long)__popcll(bal));
+}
+
+// column k0 + blockIdx.y as a segment of n entries {key of the float64 value, cell}; a left-out cell sorts behind the kept
+__global__ __launch_bounds__(256) void k_rc_vkeys(const double* __restrict__ V, int64_t n, int k0,
+                                                  const int32_t* __restrict__ codes, uint64_t* __restrict__ key,
+                                                  uint32_t* __restrict__ cell) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t at = (int64_t)blockIdx.y * n + i;
+  uint64_t k = ~0ull;
+  uint32_t cl = rs_left<uint32_t>();
+  if (codes[i] >= 0) {
+    bool is_nan;
+    k = rs_key<double>(V[(int64_t)(k0 + blockIdx.y) * n + i], &is_nan);      // (a kept cell is finite)
+    cl = (uint32_t)i;
+  }
+  key[at] = k;
+  cell[at] = cl;
+}
+
+// thread = kept position p of column k0 + blockIdx.y, whose m kept entries head its sorted segment.  The segment is sorted,
+// so the tie run [s, e) of an entry is where its key begins and ends: the entry itself when its neighbour differs, else a
+// binary search (a column is one segment of up to 2^31 entries: one workgroup walking it, as k_rs_rank walks a gene, took
+// 13 ms for a million cells).  btab[cell][column] = s + e - m; the tail of a run adds t^3 - t to the column's tie term in
+// integers, per workgroup in LDS and then once to the device's (exact and commutative: rp_add128)
+__global__ __launch_bounds__(256) void k_rc_keyrank(const uint64_t* __restrict__ key, const uint32_t* __restrict__ cell,
+                                                    int64_t n, int k0, long long m, int stride, int32_t* __restrict__ btab,
+                                                    unsigned long long* __restrict__ tie_lo, unsigned int* __restrict__ tie_hi) {
+  __shared__ unsigned long long tl;
+  __shared__ unsigned int th;
+  const int col = k0 + (int)blockIdx.y;
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  key += (int64_t)blockIdx.y * n;
+  cell += (int64_t)blockIdx.y * n;
+  if (threadIdx.x == 0) {
+    tl = 0;
+    th = 0;
+  }
+  __syncthreads();
+  if (p < m) {
+    const uint64_t kk = key[p];
+    long long s = p, e = p + 1;
+    if (p > 0 && key[p - 1] == kk) {                  // the first position of [0, p) with this key
+      long long lo = 0, hi = p - 1;
+      while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (key[mid] < kk) lo = mid + 1;
+        else hi = mid;
+      }
+      s = lo;
+    }
+    if (p + 1 < m && key[p + 1] == kk) {              // one past the last position of (p, m) with this key
+      long long lo = p + 2, hi = m;
+      while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (key[mid] > kk) hi = mid;
+        else lo = mid + 1;
+      }
+      e = lo;
+    }
+    const uint32_t cl = cell[p];
+    if ((int64_t)cl < n) btab[(int64_t)cl * stride + col] = (int32_t)(s + e - m);
+    if (e == p + 1 && e - s > 1) rp_add128(&tl, &th, rp_tie_term((unsigned long long)(e - s)));
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) rp_add128(&tie_lo[col], &tie_hi[col], {tl, (unsigned long long)th});
+}
+
+// one cell's row of btab: W columns (the least of 1, 2, 4, 8, 16 that holds q), one aligned load
+template <int W>
+struct alignas(4 * W) BRow {
+  int32_t v[W];
+};
+
+// workgroup = gene g0 + blockIdx.x over its kept[g] sorted entries {key, cell}.  a_i = s + e - m splits into a walk forward
+// (s - m, in [-m, 0)) and one backward (e, in [1, m]), found as in k_rs_rank and with its shifts by the z implicit zeros;
+// each walk gathers the entry's row and adds coefficient x b[k] -- a product below 2^62 in absolute value -- into the
+// thread's sum for column k: 64 low bits and a 32-bit count of carries less borrows (|sum| < 2^93 whatever the order).  The
+// forward walk also sums b: the implicit zeros are one group with a_0 = 2 below + t0 - m, and because b sums to 0 over the
+// kept cells their share is -a_0 x (sum of b over the stored kept entries), one 64 x 64 -> 128-bit product at the end.
+// The threads' sums are folded by a fixed tree (integers: exact in any order).  Registers: W x (2 + 1 + 2) for the sums
+// and W for the row, 96 of them at W = 16.
+template <typename K, int W>
+__global__ __launch_bounds__(RS_UNIT) void k_rc_corr(const K* __restrict__ key, const uint32_t* __restrict__ cell,
+                                                     const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,
+                                                     const unsigned int* __restrict__ kept, int64_t n, long long m, int q,
+                                                     const BRow<W>* __restrict__ btab, unsigned long long* __restrict__ s_lo,
+                                                     long long* __restrict__ s_hi, double* __restrict__ tie) {
+  constexpr K K0 = (K)1 << (8 * sizeof(K) - 1);       // the key of +0.0
+  __shared__ long long sh[RS_UNIT];
+  __shared__ double tsh[RS_UNIT];
+  __shared__ unsigned long long flo[RS_UNIT], fhi[RS_UNIT];
+  __shared__ long long fsb[RS_UNIT];
+  __shared__ unsigned int below, zeros;
+  const int t = threadIdx.x;
+  const int64_t g = g0 + blockIdx.x;
+  const long long k = (long long)kept[g], z = m - k;
+  key += seg[g] - base;
+  cell += seg[g] - base;
+  if (t == 0) below = zeros = 0;
+  __syncthreads();
+  unsigned long long lo[W];
+  int hi[W];
+  long long sb[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    lo[j] = 0;
+    hi[j] = 0;
+    sb[j] = 0;
+  }
+  const auto add = [&](long long coef, const BRow<W>& row) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const long long x = coef * (long long)row.v[j];
+      const unsigned long long old = lo[j];
+      lo[j] = old + (unsigned long long)x;
+      hi[j] += (lo[j] < old ? 1 : 0) - (x < 0 ? 1 : 0);
+    }
+  };
+  double tacc = 0.0;
+  unsigned int my_below = 0, my_zeros = 0;
+  long long carry = 0;
+  for (long long u0 = 0; u0 < k; u0 += RS_UNIT) {
+    const long long p = u0 + t;
+    const bool valid = p < k;
+    K kk = 0;
+    bool head = false, tail = false;
+    if (valid) {
+      kk = key[p];
+      head = p == 0 || key[p - 1] != kk;
+      tail = p == k - 1 || key[p + 1] != kk;
+    }
+    const long long s = rs_scan_max(head ? p : (t == 0 ? carry : -1), sh, false);
+    carry = sh[RS_UNIT - 1];
+    if (valid) {
+      const uint32_t cl = cell[p];
+      if ((int64_t)cl < n) {                          // (only a gene with a kept NaN can show a left-out entry here)
+        const BRow<W> row = btab[cl];
+        add(s + (kk > K0 ? z : 0) - m, row);
+#pragma unroll
+        for (int j = 0; j < W; ++j) sb[j] += row.v[j];
+      }
+      my_below += kk < K0 ? 1u : 0u;
+      my_zeros += kk == K0 ? 1u : 0u;
+      if (tail && kk != K0) {
+        const long long r = p + 1 - s;
+        tacc += (double)r * (double)(r * r - 1);
+      }
+    }
+    __syncthreads();                                  // sh is read (carry) before the next scan writes it
+  }
+  carry = 0;
+  for (long long u0 = k > 0 ? (k - 1) / RS_UNIT * RS_UNIT : -1; u0 >= 0; u0 -= RS_UNIT) {
+    const long long p = u0 + t;
+    const bool valid = p < k;
+    K kk = 0;
+    bool tail = false;
+    if (valid) {
+      kk = key[p];
+      tail = p == k - 1 || key[p + 1] != kk;
+    }
+    const long long none = -0x7fffffffffffffffll;
+    const long long e = -rs_scan_max(tail ? -(p + 1) : (valid && t == RS_UNIT - 1 ? carry : none), sh, true);
+    carry = sh[RS_UNIT - 1];
+    if (valid) {
+      const uint32_t cl = cell[p];
+      if ((int64_t)cl < n) add(e + (kk >= K0 ? z : 0), btab[cl]);
+    }
+    __syncthreads();
+  }
+  if (my_below) atomicAdd(&below, my_below);
+  if (my_zeros) atomicAdd(&zeros, my_zeros);
+  tsh[t] = tacc;
+  __syncthreads();
+  for (int w = RS_UNIT / 2; w > 0; w >>= 1) {
+    if (t < w) tsh[t] += tsh[t + w];
+    __syncthreads();
+  }
+  const long long t0 = (long long)zeros + z;          // the zero group: stored and implicit zeros
+  const long long a0 = 2 * (long long)below + t0 - m;
+  if (t == 0) tie[g] = tsh[0] + (t0 > 0 ? (double)t0 * (double)(t0 * t0 - 1) : 0.0);
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    if (j < q) {                                      // (q is the workgroup's: the barriers are met by all or none)
+      flo[t] = lo[j];
+      fhi[t] = (unsigned long long)(long long)hi[j];    // sign-extended: two's complement on 128 bits
+      fsb[t] = sb[j];
+      __syncthreads();
+      for (int w = RS_UNIT / 2; w > 0; w >>= 1) {
+        if (t < w) {
+          const U128 x = u128_add({flo[t], fhi[t]}, {flo[t + w], fhi[t + w]});
+          flo[t] = x.lo;
+          fhi[t] = x.hi;
+          fsb[t] += fsb[t + w];
+        }
+        __syncthreads();
+      }
+      if (t == 0) {
+        const long long na0 = -a0, B = fsb[0];
+        const U128 x = u128_add({flo[0], fhi[0]}, {(unsigned long long)na0 * (unsigned long long)B,
+                                                  (unsigned long long)__mul64hi(na0, B)});
+        s_lo[(int64_t)j * G + g] = x.lo;
+        s_hi[(int64_t)j * G + g] = (long long)x.hi;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// a chunk table of the lists' shape for `segs` segments of `len` entries each (the dense form: a gene holds the entries
+// [g n, (g + 1) n); the columns of cna_gene_rank_corr: q segments of n cells)
+int dense_table(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t len, int64_t segs, std::vector<int64_t>& seg_h,
+                std::vector<int64_t>& gchunk_h, SortTable* tb) {
+  const int64_t per = (len + RS_DENSE_CHUNK - 1) / RS_DENSE_CHUNK;
+  std::vector<int64_t> lo((size_t)(segs * per));
+  std::vector<int32_t> gene((size_t)(segs * per));
+  seg_h.resize((size_t)segs + 1);
+  gchunk_h.resize((size_t)segs + 1);
+  for (int64_t g = 0; g <= segs; ++g) {
+    seg_h[(size_t)g] = g * len;
     gchunk_h[(size_t)g] = g * per;
   }
-  for (int64_t g = 0; g < G; ++g)
+  for (int64_t g = 0; g < segs; ++g)
     for (int64_t j = 0; j < per; ++j) {
-      lo[(size_t)(g * per + j)] = g * n + j * RS_DENSE_CHUNK;
+      lo[(size_t)(g * per + j)] = g * len + j * RS_DENSE_CHUNK;
       gene[(size_t)(g * per + j)] = (int32_t)g;
     }
-  CNA_TRY(buf_need(c, s->st, w->seg, 8 * (G + 1)));
-  CNA_TRY(buf_need(c, s->st, w->gchunk, 8 * (G + 1)));
-  CNA_TRY(buf_need(c, s->st, w->chunk_lo, 8 * G * per));
-  CNA_TRY(buf_need(c, s->st, w->chunk_gene, 4 * G * per));
-  HIP_TRY(hipMemcpyAsync(w->seg.p, seg_h.data(), 8 * (size_t)(G + 1), hipMemcpyHostToDevice, s->st));
-  HIP_TRY(hipMemcpyAsync(w->gchunk.p, gchunk_h.data(), 8 * (size_t)(G + 1), hipMemcpyHostToDevice, s->st));
+  CNA_TRY(buf_need(c, s->st, w->seg, 8 * (segs + 1)));
+  CNA_TRY(buf_need(c, s->st, w->gchunk, 8 * (segs + 1)));
+  CNA_TRY(buf_need(c, s->st, w->chunk_lo, 8 * segs * per));
+  CNA_TRY(buf_need(c, s->st, w->chunk_gene, 4 * segs * per));
+  HIP_TRY(hipMemcpyAsync(w->seg.p, seg_h.data(), 8 * (size_t)(segs + 1), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemcpyAsync(w->gchunk.p, gchunk_h.data(), 8 * (size_t)(segs + 1), hipMemcpyHostToDevice, s->st));
   HIP_TRY(hipMemcpyAsync(w->chunk_lo.p, lo.data(), 8 * lo.size(), hipMemcpyHostToDevice, s->st));
   HIP_TRY(hipMemcpyAsync(w->chunk_gene.p, gene.data(), 4 * gene.size(), hipMemcpyHostToDevice, s->st));
   HIP_TRY(hipStreamSynchronize(s->st));               // the host vectors end with this scope
+  *tb = {w->seg.as<const int64_t>(), w->chunk_lo.as<const int64_t>(), w->gchunk.as<const int64_t>(),
+         w->chunk_gene.as<const int32_t>(), RS_DENSE_CHUNK};
   return 0;
 }
 
-// Tiling, keys and the radix passes, shared by both entry points: for every tile of whole genes `behind(tile, base, keys,
-// levels, seg)` queues the kernel that reads the tile's sorted lists.  `who` names the entry in what is refused.
-template <typename T, class Behind>
+// The radix passes over the chunks [c0, c0 + nch) of the segments [g0, g0 + genes) of a table, whose entries begin at
+// `base`: an even number of passes, so the sorted {key, payload} are in (ka, pa) again
+template <typename K, typename P>
+void rs_passes(hipStream_t st, const SortTable& tb, int64_t c0, int64_t nch, int64_t g0, unsigned genes, int64_t base, K* ka,
+               P* pa, K* kb, P* pb, unsigned int* cnt, unsigned int* dbase) {
+  static_assert(sizeof(K) % 2 == 0, "the result is to land where the keys were");
+  for (int pass = 0; pass < (int)sizeof(K); ++pass) {
+    const int shift = 8 * pass;
+    hipLaunchKernelGGL(k_rs_count<K>, dim3((unsigned)nch), dim3(256), 0, st, tb.chunk_lo, tb.chunk_gene, tb.seg, c0,
+                       tb.chunk_len, base, (const K*)ka, shift, cnt);
+    hipLaunchKernelGGL(k_rs_scan, dim3(genes), dim3(256), 0, st, tb.gchunk, g0, c0, cnt, dbase);
+    hipLaunchKernelGGL((k_rs_scatter<K, P>), dim3((unsigned)nch), dim3(64), 0, st, tb.chunk_lo, tb.chunk_gene, tb.seg, c0,
+                       tb.chunk_len, base, g0, (const K*)ka, (const P*)pa, kb, pb, shift, (const unsigned int*)cnt,
+                       (const unsigned int*)dbase);
+    std::swap(ka, kb);
+    std::swap(pa, pb);
+  }
+}
+
+// the sort's buffers for tiles of at most `entries` entries in `chunks` chunks of `genes` segments
+template <typename K, typename P>
+int rs_sort_bufs(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t entries, int64_t chunks, int64_t genes) {
+  CNA_TRY(buf_need(c, s->st, w->keyA, (int64_t)sizeof(K) * entries));
+  CNA_TRY(buf_need(c, s->st, w->keyB, (int64_t)sizeof(K) * entries));
+  CNA_TRY(buf_need(c, s->st, w->lvlA, (int64_t)sizeof(P) * entries));
+  CNA_TRY(buf_need(c, s->st, w->lvlB, (int64_t)sizeof(P) * entries));
+  CNA_TRY(buf_need(c, s->st, w->cnt, 4 * 256 * chunks));
+  CNA_TRY(buf_need(c, s->st, w->dbase, 4 * 256 * genes));
+  return 0;
+}
+
+// Tiling, keys and the radix passes of the resident matrix, shared by the entry points: for every tile of whole genes
+// `behind(tile, base, keys, payloads, seg)` queues the kernel that reads the tile's sorted lists.  P: what an entry carries
+// (rs_payload); the cells with codes[i] >= 0 (w->sort.code) are kept.  `who` names the entry in what is refused.
+template <typename T, typename P, class Behind>
 int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes, int64_t m, const char* who, Behind&& behind) {
   using K = typename KeyOf<T>::K;
   const int64_t n = s->n, G = s->G;
   const bool dense = s->format == 1;
   std::vector<int64_t> seg_h, gchunk_own;
-  const int64_t *seg, *chunk_lo, *gchunk;
-  const int32_t* chunk_gene;
-  int64_t chunk_len;
+  SortTable tb;
   if (dense) {
-    CNA_TRY(dense_table(c, s, w, seg_h, gchunk_own));
-    seg = w->seg.as<const int64_t>();
-    chunk_lo = w->chunk_lo.as<const int64_t>();
-    chunk_gene = w->chunk_gene.as<const int32_t>();
-    gchunk = w->gchunk.as<const int64_t>();
-    chunk_len = RS_DENSE_CHUNK;
+    CNA_TRY(dense_table(c, s, w, n, G, seg_h, gchunk_own, &tb));
   } else {
     seg_h.resize((size_t)G + 1);
     HIP_TRY(hipMemcpyAsync(seg_h.data(), s->gptr.p, 8 * (size_t)(G + 1), hipMemcpyDeviceToHost, s->st));
     HIP_TRY(hipStreamSynchronize(s->st));
-    seg = s->gptr.as<const int64_t>();
-    chunk_lo = s->chunk_lo.as<const int64_t>();
-    chunk_gene = s->chunk_gene.as<const int32_t>();
-    gchunk = s->gchunk.as<const int64_t>();
-    chunk_len = s->chunk_len;
+    tb = {s->gptr.as<const int64_t>(), s->chunk_lo.as<const int64_t>(), s->gchunk.as<const int64_t>(),
+          s->chunk_gene.as<const int32_t>(), s->chunk_len};
   }
   const std::vector<int64_t>& gchunk_h = dense ? gchunk_own : s->gchunk_h;
-  // tiles of whole genes: keys, levels and their copies within the budget
-  const int64_t per_entry = 2 * ((int64_t)sizeof(K) + 2);
+  // tiles of whole genes: keys, payloads and their copies within the budget
+  const int64_t per_entry = 2 * (int64_t)(sizeof(K) + sizeof(P));
   const int64_t max_entries = std::max<int64_t>(1, (work_bytes > 0 ? work_bytes : RS_WORK_BYTES) / per_entry);
   std::vector<GeneTile> tiles;
   int64_t most_entries = 1, most_chunks = 1, most_genes = 1;
@@ -647,12 +936,7 @@ int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes,
     most_genes = std::max(most_genes, g1 - g0);
   }
   if (most_chunks > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, std::string(who) + ": more than 2^31 - 1 chunks in one tile of genes");
-  CNA_TRY(buf_need(c, s->st, w->keyA, (int64_t)sizeof(K) * most_entries));
-  CNA_TRY(buf_need(c, s->st, w->keyB, (int64_t)sizeof(K) * most_entries));
-  CNA_TRY(buf_need(c, s->st, w->lvlA, 2 * most_entries));
-  CNA_TRY(buf_need(c, s->st, w->lvlB, 2 * most_entries));
-  CNA_TRY(buf_need(c, s->st, w->cnt, 4 * 256 * most_chunks));
-  CNA_TRY(buf_need(c, s->st, w->dbase, 4 * 256 * most_genes));
+  CNA_TRY((rs_sort_bufs<K, P>(c, s, w, most_entries, most_chunks, most_genes)));
   CNA_TRY(buf_need(c, s->st, w->kept, 4 * G));
   CNA_TRY(buf_need(c, s->st, w->nanf, 4 * G));
   HIP_TRY(hipMemsetAsync(w->nanf.p, 0, (size_t)(4 * G), s->st));
@@ -664,7 +948,7 @@ int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes,
     HIP_TRY(hipMemsetAsync(w->kept.p, 0, (size_t)(4 * G), s->st));
   }
   K *ka = w->keyA.as<K>(), *kb = w->keyB.as<K>();
-  uint16_t *la = w->lvlA.as<uint16_t>(), *lb = w->lvlB.as<uint16_t>();
+  P *la = w->lvlA.as<P>(), *lb = w->lvlB.as<P>();
   unsigned int *cnt = w->cnt.as<unsigned int>(), *dbase = w->dbase.as<unsigned int>();
   for (const GeneTile& t : tiles) {
     const int64_t base = seg_h[(size_t)t.g0];
@@ -673,28 +957,18 @@ int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes,
       {
         ProfScope ps(c, CNA_K_RANKSUM_KEYS, s->st);
         if (dense)
-          hipLaunchKernelGGL(k_rs_keys_dense<T>, dim3((unsigned)((n + RS_TILE - 1) / RS_TILE), (genes + RS_TILE - 1) / RS_TILE),
+          hipLaunchKernelGGL((k_rs_keys_dense<T, P>), dim3((unsigned)((n + RS_TILE - 1) / RS_TILE), (genes + RS_TILE - 1) / RS_TILE),
                              dim3(256), 0, s->st, s->X.as<const T>(), n, G, t.g0, t.g1, w->sort.codes(), base, ka, la,
                              w->nanf.as<unsigned int>());
         else
-          hipLaunchKernelGGL(k_rs_keys_sparse<T>, dim3((unsigned)t.nch), dim3(256), 0, s->st, chunk_lo, chunk_gene, seg, t.c0,
-                             chunk_len, s->gcell.as<const int32_t>(), s->gval.as<const T>(), w->sort.codes(), base, ka, la,
-                             w->kept.as<unsigned int>(), w->nanf.as<unsigned int>());
+          hipLaunchKernelGGL((k_rs_keys_sparse<T, P>), dim3((unsigned)t.nch), dim3(256), 0, s->st, tb.chunk_lo, tb.chunk_gene,
+                             tb.seg, t.c0, tb.chunk_len, s->gcell.as<const int32_t>(), s->gval.as<const T>(), w->sort.codes(),
+                             base, ka, la, w->kept.as<unsigned int>(), w->nanf.as<unsigned int>());
       }
       ProfScope ps(c, CNA_K_RANKSUM_SORT, s->st);
-      for (int pass = 0; pass < (int)sizeof(K); ++pass) {         // an even number of passes: the result is in A again
-        const int shift = 8 * pass;
-        hipLaunchKernelGGL(k_rs_count<K>, dim3((unsigned)t.nch), dim3(256), 0, s->st, chunk_lo, chunk_gene, seg, t.c0, chunk_len,
-                           base, (const K*)ka, shift, cnt);
-        hipLaunchKernelGGL(k_rs_scan, dim3(genes), dim3(256), 0, s->st, gchunk, t.g0, t.c0, cnt, dbase);
-        hipLaunchKernelGGL(k_rs_scatter<K>, dim3((unsigned)t.nch), dim3(64), 0, s->st, chunk_lo, chunk_gene, seg, t.c0, chunk_len,
-                           base, t.g0, (const K*)ka, (const uint16_t*)la, kb, lb, shift, (const unsigned int*)cnt,
-                           (const unsigned int*)dbase);
-        std::swap(ka, kb);
-        std::swap(la, lb);
-      }
+      rs_passes<K, P>(s->st, tb, t.c0, t.nch, t.g0, genes, base, ka, la, kb, lb, cnt, dbase);
     }
-    behind(t, base, (const K*)ka, (const uint16_t*)la, seg);
+    behind(t, base, (const K*)ka, (const P*)la, tb.seg);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -706,7 +980,7 @@ int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t wo
   const int64_t G = s->G;
   CNA_TRY(buf_need(c, s->st, w->rank2, 8 * (int64_t)n_bins * G));
   CNA_TRY(buf_need(c, s->st, w->tie, 8 * G));
-  return ranksum_sorted<T>(c, s, w, work_bytes, m, "cna_gene_ranksum_by",
+  return ranksum_sorted<T, uint16_t>(c, s, w, work_bytes, m, "cna_gene_ranksum_by",
                            [&](const GeneTile& t, int64_t base, const K* key, const uint16_t* lvl, const int64_t* seg) {
                              ProfScope ps(c, CNA_K_RANKSUM_RANK, s->st);
                              hipLaunchKernelGGL(k_rs_rank<K>, dim3((unsigned)(t.g1 - t.g0)), dim3(RS_UNIT), 0, s->st, key, lvl, seg,
@@ -719,7 +993,7 @@ template <typename T>
 int pairs_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int n_pairs, int64_t work_bytes, int64_t m) {
   using K = typename KeyOf<T>::K;
   const int64_t G = s->G;
-  return ranksum_sorted<T>(c, s, w, work_bytes, m, "cna_gene_ranksum_pairs",
+  return ranksum_sorted<T, uint16_t>(c, s, w, work_bytes, m, "cna_gene_ranksum_pairs",
                            [&](const GeneTile& t, int64_t base, const K* key, const uint16_t* lvl, const int64_t* seg) {
                              ProfScope ps(c, CNA_K_RANKSUM_PAIRS, s->st);
                              hipLaunchKernelGGL(k_rs_pairs<K>, dim3((unsigned)(t.g1 - t.g0)), dim3(RS_UNIT), 0, s->st, key, lvl, seg,
@@ -727,6 +1001,62 @@ int pairs_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int n_pairs,
                                                 n_bins, w->pairs.as<const int32_t>(), n_pairs, w->u2.as<long long>(),
                                                 w->ptie.as<double>());
                            });
+}
+
+// The columns' ranks: tiles of whole columns within the budget, each a segment of n entries in a table of the dense form's
+// shape; sorted by the same passes, then k_rc_keyrank writes btab and the tie terms
+int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, int64_t work_bytes, int64_t m) {
+  const int64_t n = s->n, per = (n + RS_DENSE_CHUNK - 1) / RS_DENSE_CHUNK;
+  const int64_t per_entry = 2 * (int64_t)(sizeof(uint64_t) + sizeof(uint32_t));
+  const int64_t max_entries = std::max<int64_t>(1, (work_bytes > 0 ? work_bytes : RS_WORK_BYTES) / per_entry);
+  const int cols = (int)std::min<int64_t>(q, std::max<int64_t>(1, max_entries / n));
+  if (cols * per > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: more than 2^31 - 1 chunks in one tile of columns");
+  std::vector<int64_t> seg_h, gchunk_h;
+  SortTable tb;
+  CNA_TRY(dense_table(c, s, w, n, q, seg_h, gchunk_h, &tb));
+  CNA_TRY((rs_sort_bufs<uint64_t, uint32_t>(c, s, w, cols * n, cols * per, cols)));
+  uint64_t *ka = w->keyA.as<uint64_t>(), *kb = w->keyB.as<uint64_t>();
+  uint32_t *pa = w->lvlA.as<uint32_t>(), *pb = w->lvlB.as<uint32_t>();
+  for (int k0 = 0; k0 < q; k0 += cols) {
+    const int k1 = std::min(q, k0 + cols);
+    {
+      ProfScope ps(c, CNA_K_RANKSUM_KEYS, s->st);
+      hipLaunchKernelGGL(k_rc_vkeys, dim3((unsigned)((n + 255) / 256), (unsigned)(k1 - k0)), dim3(256), 0, s->st,
+                         w->vcol.as<const double>(), n, k0, w->sort.codes(), ka, pa);
+    }
+    {
+      ProfScope ps(c, CNA_K_RANKSUM_SORT, s->st);
+      rs_passes<uint64_t, uint32_t>(s->st, tb, k0 * per, (k1 - k0) * per, k0, (unsigned)(k1 - k0), k0 * n, ka, pa, kb, pb,
+                                    w->cnt.as<unsigned int>(), w->dbase.as<unsigned int>());
+    }
+    ProfScope ps(c, CNA_K_RANKCORR_KEYS, s->st);
+    if (m > 0)
+      hipLaunchKernelGGL(k_rc_keyrank, dim3((unsigned)((m + 255) / 256), (unsigned)(k1 - k0)), dim3(256), 0, s->st,
+                         (const uint64_t*)ka, (const uint32_t*)pa, n, k0, (long long)m, stride, w->btab.as<int32_t>(),
+                         w->tiek.as<unsigned long long>(), w->tiek.as<unsigned int>() + 2 * RC_MAX_KEYS);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int rankcorr_run(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int64_t work_bytes, int64_t m) {
+  using K = typename KeyOf<T>::K;
+  const int64_t G = s->G, n = s->n;
+  int rc = 0;
+  with_width(q, [&](auto width) {
+    constexpr int W = decltype(width)::value;
+    rc = ranksum_sorted<T, uint32_t>(c, s, w, work_bytes, m, "cna_gene_rank_corr",
+                                     [&](const GeneTile& t, int64_t base, const K* key, const uint32_t* cell, const int64_t* seg) {
+                                       ProfScope ps(c, CNA_K_RANKCORR_CORR, s->st);
+                                       hipLaunchKernelGGL((k_rc_corr<K, W>), dim3((unsigned)(t.g1 - t.g0)), dim3(RS_UNIT), 0, s->st,
+                                                          key, cell, seg, base, t.g0, G, w->kept.as<const unsigned int>(), n,
+                                                          (long long)m, q, w->btab.as<const BRow<W>>(),
+                                                          w->slo.as<unsigned long long>(), w->shi.as<long long>(),
+                                                          w->tie.as<double>());
+                                     });
+  });
+  return rc;
 }
 
 }  // namespace
@@ -801,5 +1131,61 @@ extern "C" int cna_gene_ranksum_pairs(cna_ctx* c, const int32_t* codes, int n_bi
   }
   for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
   for (int b = 0; b < n_bins; ++b) n_out[b] = w->sort.tot_h[(size_t)b];
+  return 0;
+}
+
+extern "C" int cna_gene_rank_corr(cna_ctx* c, const double* V, int q, int64_t work_bytes, uint64_t* s_lo, int64_t* s_hi,
+                                  double* tie_gene, double* tie_key, int64_t* m_out, uint8_t* nan_out) {
+  CHECK_CTX(c);
+  ExprState* s = expr_state(c);
+  if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_gene_rank_corr: no expression matrix is resident (cna_expr_upload_*)");
+  if (!V || !s_lo || !s_hi || !tie_gene || !tie_key || !m_out || !nan_out) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: null pointer");
+  if (q < 1 || q > RC_MAX_KEYS) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: 1 <= q <= 16");
+  if (work_bytes < 0) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: work_bytes is 0 (the default) or a number of bytes");
+  const int64_t G = s->G, n = s->n;
+  int stride = 1;
+  with_width(q, [&](auto width) { stride = decltype(width)::value; });
+  RankSumWork* w = expr_work<RankSumWork>(s, EXPR_RANKSUM);
+  CNA_TRY(buf_need(c, s->st, w->vcol, 8 * (int64_t)q * n));
+  CNA_TRY(buf_need(c, s->st, w->sort.code, 4 * n));
+  CNA_TRY(buf_need(c, s->st, w->vm, 8));
+  CNA_TRY(buf_need(c, s->st, w->btab, 4 * (int64_t)stride * n));
+  CNA_TRY(buf_need(c, s->st, w->tiek, 12 * RC_MAX_KEYS));   // per column 64 low bits, then 32 high bits, of its tie term
+  CNA_TRY(buf_need(c, s->st, w->slo, 8 * (int64_t)q * G));
+  CNA_TRY(buf_need(c, s->st, w->shi, 8 * (int64_t)q * G));
+  CNA_TRY(buf_need(c, s->st, w->tie, 8 * G));
+  unsigned long long m_dev = 0;
+  {
+    // the kept cells: every column finite.  The rows of btab of the other cells, and its columns from q on, are never
+    // meant: zero, so that what the gather reads of them is defined
+    ProfScope ps(c, CNA_K_RANKCORR_KEYS, s->st);
+    HIP_TRY(hipMemcpyAsync(w->vcol.p, V, (size_t)(8 * (int64_t)q * n), hipMemcpyHostToDevice, s->st));
+    HIP_TRY(hipMemsetAsync(w->vm.p, 0, 8, s->st));
+    HIP_TRY(hipMemsetAsync(w->tiek.p, 0, 12 * RC_MAX_KEYS, s->st));
+    HIP_TRY(hipMemsetAsync(w->btab.p, 0, (size_t)(4 * (int64_t)stride * n), s->st));
+    hipLaunchKernelGGL(k_rc_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, w->vcol.as<const double>(), q, n,
+                       w->sort.code.as<int32_t>(), w->vm.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&m_dev, w->vm.p, 8, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));             // the caller has its columns back
+  }
+  const int64_t m = (int64_t)m_dev;
+  CNA_TRY(rankcorr_keys(c, s, w, q, stride, work_bytes, m));
+  if (s->is_f64) CNA_TRY(rankcorr_run<double>(c, s, w, q, work_bytes, m));
+  else CNA_TRY(rankcorr_run<float>(c, s, w, q, work_bytes, m));
+  std::vector<unsigned int> nanf((size_t)G);
+  unsigned long long tie_words[RC_MAX_KEYS + RC_MAX_KEYS / 2];
+  {
+    ProfScope ps(c, CNA_K_RANKSUM_FETCH, s->st);
+    CNA_TRY(fetch_results(s->st, "cna_gene_rank_corr", {{s_lo, w->slo.p, (size_t)(8 * (int64_t)q * G)},
+                                                       {s_hi, w->shi.p, (size_t)(8 * (int64_t)q * G)},
+                                                       {tie_gene, w->tie.p, (size_t)(8 * G)},
+                                                       {tie_words, w->tiek.p, sizeof(tie_words)},
+                                                       {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
+  }
+  for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
+  const unsigned int* tie_high = reinterpret_cast<const unsigned int*>(tie_words + RC_MAX_KEYS);
+  for (int k = 0; k < q; ++k) tie_key[k] = (double)tie_high[k] * 18446744073709551616.0 + (double)tie_words[k];   // rounded once
+  *m_out = m;
   return 0;
 }

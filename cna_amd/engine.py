@@ -1368,6 +1368,28 @@ class Engine(_order.CellOrder):
                                               ptr(tie), ptr(n), ptr(nan)), 'cna_gene_ranksum_pairs')
         return u2, tie, n, nan.astype(bool)
 
+    def gene_rank_corr(self, V, work_bytes=0):
+        """The integers of Spearman's rank correlation of every gene of the resident expression matrix with every row of V
+        (q x cells float64, caller's cell order, 1 <= q <= 16; a cell where any row is non-finite is left out of the whole
+        call), midranks over the m kept cells (cna_gene_rank_corr).  `work_bytes` bounds the sort's entries of one tile of
+        genes (0: the library's default).  Returns (s_lo uint64[q, genes], s_hi int64[q, genes]: S = sum of (2 r_gene - (m +
+        1)) (2 r_key - (m + 1)) in 128-bit two's complement, tie_gene float64[genes], tie_key float64[q]: sum of t^3 - t over
+        the tie groups, m int, nan bool[genes]: a kept cell holds NaN and the gene's numbers mean nothing)."""
+        V = _f64(V)
+        info = self.expression_shape()
+        if info['format'] != 'none' and (V.ndim != 2 or V.shape[1] != info['n_cells']):
+            raise ValueError('gene_rank_corr: keys %s for %d resident cells' % (V.shape, info['n_cells']))
+        q = int(V.shape[0]) if V.ndim == 2 else 0
+        s_lo = np.empty((max(q, 0), info['n_genes']), dtype=np.uint64)
+        s_hi = np.empty((max(q, 0), info['n_genes']), dtype=np.int64)
+        tie_gene = np.empty(info['n_genes'])
+        tie_key = np.empty(max(q, 0))
+        m = C.c_int64(0)
+        nan = np.empty(info['n_genes'], dtype=np.uint8)
+        check(self.lib.cna_gene_rank_corr(self.h, ptr(V), q, int(work_bytes), ptr(s_lo), ptr(s_hi), ptr(tie_gene), ptr(tie_key),
+                                          C.byref(m), ptr(nan)), 'cna_gene_rank_corr')
+        return s_lo, s_hi, tie_gene, tie_key, int(m.value), nan.astype(bool)
+
     BW_KINDS = ('scott', 'silverman', 'constant')
 
     def coef_strata(self, v, fdr, codes, n_bins, fdr_thresh, points, bw_kind='scott', bw_value=0.0):
@@ -1727,7 +1749,7 @@ class Engine(_order.CellOrder):
     def prof(self):
         """{kernel name: (total ms, launches)} for kernels launched while profiling was on."""
         out = {}
-        for k, name in enumerate(_ffi.KERNELS):
+        for k, name in enumerate(_ffi.KERNELS + _ffi.KERNELS_RANK_CORR):
             ms, n = C.c_double(0.0), C.c_int64(0)
             check(self.lib.cna_prof_get(self.h, k, C.byref(ms), C.byref(n)), 'cna_prof_get')
             if n.value:

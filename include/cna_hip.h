@@ -82,6 +82,10 @@ enum {
   /* cna_gene_ranksum_pairs: the kernel behind the sort (the keys, the sort and the copies back are counted under the ids
    * above) */
   CNA_K_RANKSUM_PAIRS,
+  /* cna_gene_rank_corr: the ranks of the columns (their upload, the kept cells, the kernel behind their sort) and the
+   * correlation kernel behind the genes' sort; the keys, both sorts and the copies back are counted under
+   * CNA_K_RANKSUM_KEYS, _SORT and _FETCH */
+  CNA_K_RANKCORR_KEYS, CNA_K_RANKCORR_CORR,
   CNA_K_COUNT
 };
 
@@ -631,7 +635,7 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
  * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster, cna_graph_components_find,
- * cna_gene_ranksum_by and cna_gene_ranksum_pairs: cna_ctx_device_bytes returns to what it was before the upload. */
+ * cna_gene_ranksum_by, cna_gene_ranksum_pairs and cna_gene_rank_corr: cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -777,6 +781,39 @@ int  cna_gene_ranksum_by(cna_ctx* ctx, const int32_t* codes, int n_bins, int64_t
  * not fit; the context stays usable. */
 int  cna_gene_ranksum_pairs(cna_ctx* ctx, const int32_t* codes, int n_bins, const int32_t* pairs, int n_pairs,
                             int64_t work_bytes, int64_t* u2_out, double* tie_out, int64_t* n_out, uint8_t* nan_out);
+
+/* Spearman's rank correlation of every gene with 1 <= q <= 16 per-cell columns (cna.tl.gene_rank_corr), from the same sort
+ * with the cell as the entry's payload: invariant to log1p, scaling and every other monotone normalisation of X or of a
+ * column, which cna_gene_corr's Pearson r is not.
+ *   V[k * n_cells + i]  column k in cell i (CALLER's cell order).  The m KEPT cells are those where EVERY column is finite:
+ *             one set per call (a gene's ranks depend on the set), unlike cna_gene_corr's set per column
+ *   work_bytes  as in cna_gene_ranksum_by, for {key, cell} entries: 2 x (4 or 8, + 4) bytes each; the columns are sorted
+ *             within the same budget, q segments of n_cells entries of 2 x (8 + 4) bytes, one column at least at a time
+ * Genes and columns are ranked over the kept cells with midranks: a gene on the stored type's bits by the rules of
+ * cna_gene_ranksum_by (-0.0 = +0.0 = a stored zero = the implicit zeros, +-inf ordinary, float64 on 64 bits), a column as
+ * float64 on all 64 bits with -0.0 = +0.0.  With r the midrank, a_i = 2 r_gene(i) - (m + 1) and b_i = 2 r_column(i) -
+ * (m + 1): integers below m in absolute value that sum to 0 over the kept cells.
+ *   s_lo_out[k * n_genes + g], s_hi_out[k * n_genes + g]   S = sum over the kept cells of a_i b_i in 128-bit two's
+ *             complement: the low 64 bits and the limb above them.  |S| <= (m^3 - m) / 3, which passes 2^63 from
+ *             3 024 617 cells on; nothing is rounded and no m is refused
+ *   tie_gene_out[g]   sum over the tie groups of t^3 - t, formed like cna_gene_ranksum_by's tie_out
+ *   tie_key_out[k]    the same for column k, summed in integers (96 bits) and rounded to double once: exact below 2^53
+ *   *m_out = m;  nan_out[g] as in cna_gene_ranksum_by (the gene's other outputs are then unspecified)
+ * so that rho = 3 S / sqrt((m^3 - m - tie_gene) (m^3 - m - tie_key)), scipy.stats.spearmanr's statistic; the float64
+ * line is the caller's (cna_amd/tools/_gene_rank_corr.py: rank_corr_statistics), with NaN for a constant gene or column
+ * (tie = m^3 - m), m < 2 and a flagged gene.  No p-value: cells are not independent (cna.tl.gene_test).
+ * One thread per kept entry of a column finds its tie run [s, e) in the column's sorted segment (a binary search where a
+ * neighbour ties) and writes b = s + e - m into a cell-major table; one workgroup per gene walks the gene's sorted list forward for s and backward for e, gathers
+ * the cell's row of that table and adds coefficient x b per column in integer registers, folded in a fixed order; the
+ * implicit zeros of the gene-major form are one group whose share is -a_0 x (sum of b over the stored kept entries).
+ * The same bits on every run, under every work_bytes and for a CSR and a CSC upload of one matrix.
+ * Runs on the expression stream with the work buffers of cna_gene_ranksum_by (grow-only, freed by cna_expr_drop), changes
+ * no other state, works on a context that never saw a graph and may be called between cna_null_local_launch and
+ * cna_null_local_fetch.
+ * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL, with nothing written: a null pointer, q outside [1, 16] or
+ * a negative work_bytes. */
+int  cna_gene_rank_corr(cna_ctx* ctx, const double* V, int q, int64_t work_bytes, uint64_t* s_lo_out, int64_t* s_hi_out,
+                        double* tie_gene_out, double* tie_key_out, int64_t* m_out, uint8_t* nan_out);
 
 /* ---- the expression matrix against the working matrix (csrc/expr_cross.hip) ------------------- */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
