@@ -46,6 +46,14 @@
 // half with the coefficient it has in hand and nothing about an open run is carried from unit to unit but its start; the
 // price is the second gather of the row, which comes from the same table in reverse order)
 //
+// cna_gene_rank_corr_by: the same inside every level of a clustering (cna.tl.gene_rank_corr_strata), from one sort.  The
+// kept cells keep their level (k_rc_mask<true>: the level as a byte per cell, the kept cells per level); behind the value
+// passes one more stable pass takes that byte as its digit (DigitOfLevel; 255: a left-out entry), so a gene's list, and a
+// column's segment, is level-major and sorted by value inside a level, and the scan of that pass (dbase) says where every
+// (segment, level) begins.  k_rc_keyrank<true> keeps its searches inside the level's range and k_rc_corr runs once per
+// (gene, level) on the sub-segment (GeneLevel) with the level's m_l, k_l and z_l: level l is cna_gene_rank_corr on columns
+// set to NaN outside l, integer for integer.  The pass count is odd: the sorted lists are in the other buffer of each pair.
+//
 // The genes go in tiles of whole genes whose keys, payloads and their ping-pong copies stay within work_bytes (0:
 // RS_WORK_BYTES); a gene that alone exceeds it is one tile.  The counters of the sort (1 KB per chunk) come on top.
 #include "expr.h"
@@ -59,6 +67,7 @@ constexpr int RS_UNIT = 256;                   // entries of a gene's sorted lis
 constexpr int RS_TILE = 64;                    // the dense gather's square tile
 constexpr uint16_t RS_LEFT = 0xffff;           // "level" of an entry whose cell is left out (rs_left<uint16_t>())
 constexpr int RC_MAX_KEYS = 16;                // cna_gene_rank_corr: per-cell columns of one call
+constexpr int RC_MAX_LEVELS = 255;             // cna_gene_rank_corr_by: the level is a digit of the sort, 255 = left out
 constexpr int RP_MAX_LEVELS = 64;              // cna_gene_ranksum_pairs: levels that take part,
 constexpr int RP_SLOTS = 2016;                 // their unordered pairs (the accumulators in LDS) and
 constexpr int RP_MAX_PAIRS = 2016;             // the pairs of one call
@@ -75,6 +84,7 @@ struct RankSumWork : BufSet {
   Buf seg{*this}, chunk_lo{*this}, chunk_gene{*this}, gchunk{*this};   // the dense form's table (the lists have the state's)
   // cna_gene_rank_corr: the columns, the kept cells' count, b[cell][W], the columns' tie terms (96 bits), the two limbs of S
   Buf vcol{*this}, vm{*this}, btab{*this}, tiek{*this}, slo{*this}, shi{*this};
+  Buf lvl8{*this};                                                     // cna_gene_rank_corr_by: the kept cell's level as a byte
 };
 
 // What an entry carries through the sort beside its key: the level of its cell (uint16_t: the rank sums) or the cell
@@ -196,18 +206,33 @@ __global__ __launch_bounds__(256) void k_rs_keys_dense(const T* __restrict__ X, 
 }
 
 // ------------------------------------------------------------------ the sort: one pass of 8 bits
+// Where a pass takes its digit from: 8 bits of the key (the value passes), or the level of the entry's cell from a byte
+// per cell (the one pass behind them in cna_gene_rank_corr_by; the payload is the cell, 255 = a left-out entry).  What a
+// source does not read of an entry is not loaded.
+template <typename K, typename P>
+struct DigitOfKey {
+  int shift;
+  __device__ __forceinline__ unsigned int operator()(K k, P) const { return (unsigned)(k >> shift) & 255u; }
+};
+template <typename K, typename P>
+struct DigitOfLevel {
+  const uint8_t* lvl8;
+  __device__ __forceinline__ unsigned int operator()(K, P cell) const { return cell == rs_left<P>() ? 255u : (unsigned)lvl8[cell]; }
+};
+
 // cnt[chunk - c0][digit] = entries of the chunk with that digit
-template <typename K>
+template <typename K, typename P, class D>
 __global__ __launch_bounds__(256) void k_rs_count(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
                                                   const int64_t* __restrict__ seg, int64_t c0, int64_t chunk_len, int64_t base,
-                                                  const K* __restrict__ key, int shift, unsigned int* __restrict__ cnt) {
+                                                  const K* __restrict__ key, const P* __restrict__ pay, D digit,
+                                                  unsigned int* __restrict__ cnt) {
   __shared__ unsigned int h[256];
   h[threadIdx.x] = 0;
   __syncthreads();
   const int64_t ch = c0 + blockIdx.x;
   const int64_t lo = chunk_lo[ch], end = seg[chunk_gene[ch] + 1];
   const int64_t hi = lo + chunk_len < end ? lo + chunk_len : end;
-  for (int64_t e = lo + threadIdx.x; e < hi; e += blockDim.x) atomicAdd(&h[(unsigned)(key[e - base] >> shift) & 255u], 1u);
+  for (int64_t e = lo + threadIdx.x; e < hi; e += blockDim.x) atomicAdd(&h[digit(key[e - base], pay[e - base])], 1u);
   __syncthreads();
   cnt[(int64_t)blockIdx.x * 256 + threadIdx.x] = h[threadIdx.x];
 }
@@ -240,11 +265,11 @@ __global__ __launch_bounds__(256) void k_rs_scan(const int64_t* __restrict__ gch
 
 // one wave per chunk; cur[digit] = where the chunk's next entry with that digit goes inside the gene's segment.  In a batch
 // of 64 entries the lanes with one digit find each other with 8 ballots and take consecutive places in lane order.
-template <typename K, typename P>
+template <typename K, typename P, class D>
 __global__ __launch_bounds__(64) void k_rs_scatter(const int64_t* __restrict__ chunk_lo, const int32_t* __restrict__ chunk_gene,
                                                    const int64_t* __restrict__ seg, int64_t c0, int64_t chunk_len, int64_t base,
                                                    int64_t g0, const K* __restrict__ kin, const P* __restrict__ lin,
-                                                   K* __restrict__ kout, P* __restrict__ lout, int shift,
+                                                   K* __restrict__ kout, P* __restrict__ lout, D digit,
                                                    const unsigned int* __restrict__ cnt, const unsigned int* __restrict__ dbase) {
   __shared__ unsigned int cur[256];
   const int lane = threadIdx.x;
@@ -263,7 +288,7 @@ __global__ __launch_bounds__(64) void k_rs_scatter(const int64_t* __restrict__ c
       k = kin[e - base];
       l = lin[e - base];
     }
-    const unsigned int d = (unsigned)(k >> shift) & 255u;
+    const unsigned int d = digit(k, l);               // (a lane past the end: entry 0's, and never used)
     unsigned long long same = __ballot(valid);
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
@@ -619,17 +644,36 @@ __global__ __launch_bounds__(RS_UNIT) void k_rs_pairs(const K* __restrict__ key,
 //   S[k, g] = sum over the kept cells of a_i b_i[k]      rho = 3 S / sqrt((m^3 - m - T_g) (m^3 - m - T_k))   (the host's line)
 // |S| <= (m^3 - m) / 3 passes 2^63 from 3 024 617 cells on, so S is summed and returned in 128 bits.
 
-// codes[i] = 0 where every column is finite, else -1; *m += their number
+// codes[i] = 0 where every column is finite, else -1; *m += their number.  BY (cna_gene_rank_corr_by): codes holds the
+// caller's levels, all in [-1, n_bins) with n_bins <= 255; a cell keeps its level where every column is finite, else -1;
+// lvl8[i] = that level as a byte, 255 for -1 (the digit of the sort's last pass); m[l] += the kept cells of level l
+template <bool BY>
 __global__ __launch_bounds__(256) void k_rc_mask(const double* __restrict__ V, int q, int64_t n, int32_t* __restrict__ codes,
-                                                 unsigned long long* __restrict__ m) {
+                                                 uint8_t* __restrict__ lvl8, unsigned long long* __restrict__ m) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool keep = i < n;
-  if (i < n) {
-    for (int k = 0; k < q; ++k) keep = keep && finite_d(V[(int64_t)k * n + i]);
-    codes[i] = keep ? 0 : -1;
+  if constexpr (BY) {
+    __shared__ unsigned int h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    if (i < n) {
+      const int32_t cd = codes[i];
+      keep = cd >= 0;
+      for (int k = 0; k < q; ++k) keep = keep && finite_d(V[(int64_t)k * n + i]);
+      codes[i] = keep ? cd : -1;
+      lvl8[i] = keep ? (uint8_t)cd : (uint8_t)255;
+      if (keep) atomicAdd(&h[cd & 255], 1u);
+    }
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&m[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+  } else {
+    if (i < n) {
+      for (int k = 0; k < q; ++k) keep = keep && finite_d(V[(int64_t)k * n + i]);
+      codes[i] = keep ? 0 : -1;
+    }
+    const unsigned long long bal = __ballot(keep);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(m, (unsigned long long)__popcll(bal));
   }
-  const unsigned long long bal = __ballot(keep);
-  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(m, (unsigned long long)__popcll(bal));
 }
 
 // column k0 + blockIdx.y as a segment of n entries {key of the float64 value, cell}; a left-out cell sorts behind the kept
@@ -654,12 +698,19 @@ __global__ __launch_bounds__(256) void k_rc_vkeys(const double* __restrict__ V, 
 // so the tie run [s, e) of an entry is where its key begins and ends: the entry itself when its neighbour differs, else a
 // binary search (a column is one segment of up to 2^31 entries: one workgroup walking it, as k_rs_rank walks a gene, took
 // 13 ms for a million cells).  btab[cell][column] = s + e - m; the tail of a run adds t^3 - t to the column's tie term in
-// integers, per workgroup in LDS and then once to the device's (exact and commutative: rp_add128)
+// integers, per workgroup in LDS and then once to the device's (exact and commutative: rp_add128).
+// BY (cna_gene_rank_corr_by): the segment is level-major behind the sort's last pass and level l of this column is its
+// positions [dbase[l], dbase[l + 1]): the entry is ranked inside its level -- the searches stay in that range, so a run ends
+// where the level does -- and b = s + e - 2 start - m_l; the tie terms are kept per level, tie[l][column], the workgroup's
+// LDS sum serving the level of its first entry and the few entries of a later level adding to the device's themselves.
+template <bool BY>
 __global__ __launch_bounds__(256) void k_rc_keyrank(const uint64_t* __restrict__ key, const uint32_t* __restrict__ cell,
                                                     int64_t n, int k0, long long m, int stride, int32_t* __restrict__ btab,
-                                                    unsigned long long* __restrict__ tie_lo, unsigned int* __restrict__ tie_hi) {
+                                                    unsigned long long* __restrict__ tie_lo, unsigned int* __restrict__ tie_hi,
+                                                    const uint8_t* __restrict__ lvl8, const unsigned int* __restrict__ dbase) {
   __shared__ unsigned long long tl;
   __shared__ unsigned int th;
+  __shared__ int first_level;
   const int col = k0 + (int)blockIdx.y;
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   key += (int64_t)blockIdx.y * n;
@@ -667,13 +718,27 @@ __global__ __launch_bounds__(256) void k_rc_keyrank(const uint64_t* __restrict__
   if (threadIdx.x == 0) {
     tl = 0;
     th = 0;
+    first_level = 0;
+    if constexpr (BY) {
+      if (p < m && (int64_t)cell[p] < n) first_level = (int)lvl8[cell[p]];
+    }
   }
   __syncthreads();
   if (p < m) {
     const uint64_t kk = key[p];
+    const uint32_t cl = cell[p];
+    long long from = 0, to = m;                       // the positions the entry is ranked among
+    int level = 0;
+    if constexpr (BY) {
+      level = (int64_t)cl < n ? (int)lvl8[cl] : 255;
+      if (level < 255) {                              // (a kept entry: the first m of the segment are)
+        from = (long long)dbase[(int64_t)blockIdx.y * 256 + level];
+        to = (long long)dbase[(int64_t)blockIdx.y * 256 + level + 1];
+      }
+    }
     long long s = p, e = p + 1;
-    if (p > 0 && key[p - 1] == kk) {                  // the first position of [0, p) with this key
-      long long lo = 0, hi = p - 1;
+    if (p > from && key[p - 1] == kk) {               // the first position of [from, p) with this key
+      long long lo = from, hi = p - 1;
       while (lo < hi) {
         const long long mid = (lo + hi) >> 1;
         if (key[mid] < kk) lo = mid + 1;
@@ -681,8 +746,8 @@ __global__ __launch_bounds__(256) void k_rc_keyrank(const uint64_t* __restrict__
       }
       s = lo;
     }
-    if (p + 1 < m && key[p + 1] == kk) {              // one past the last position of (p, m) with this key
-      long long lo = p + 2, hi = m;
+    if (p + 1 < to && key[p + 1] == kk) {             // one past the last position of (p, to) with this key
+      long long lo = p + 2, hi = to;
       while (lo < hi) {
         const long long mid = (lo + hi) >> 1;
         if (key[mid] > kk) hi = mid;
@@ -690,12 +755,15 @@ __global__ __launch_bounds__(256) void k_rc_keyrank(const uint64_t* __restrict__
       }
       e = lo;
     }
-    const uint32_t cl = cell[p];
-    if ((int64_t)cl < n) btab[(int64_t)cl * stride + col] = (int32_t)(s + e - m);
-    if (e == p + 1 && e - s > 1) rp_add128(&tl, &th, rp_tie_term((unsigned long long)(e - s)));
+    if ((int64_t)cl < n) btab[(int64_t)cl * stride + col] = (int32_t)(s + e - 2 * from - (to - from));
+    if (e == p + 1 && e - s > 1) {
+      const U128 term = rp_tie_term((unsigned long long)(e - s));
+      if (level == first_level) rp_add128(&tl, &th, term);
+      else if (level < 255) rp_add128(&tie_lo[level * RC_MAX_KEYS + col], &tie_hi[level * RC_MAX_KEYS + col], term);
+    }
   }
   __syncthreads();
-  if (threadIdx.x == 0) rp_add128(&tie_lo[col], &tie_hi[col], {tl, (unsigned long long)th});
+  if (threadIdx.x == 0) rp_add128(&tie_lo[first_level * RC_MAX_KEYS + col], &tie_hi[first_level * RC_MAX_KEYS + col], {tl, (unsigned long long)th});
 }
 
 // one cell's row of btab: W columns (the least of 1, 2, 4, 8, 16 that holds q), one aligned load
@@ -712,10 +780,35 @@ struct alignas(4 * W) BRow {
 // kept cells their share is -a_0 x (sum of b over the stored kept entries), one 64 x 64 -> 128-bit product at the end.
 // The threads' sums are folded by a fixed tree (integers: exact in any order).  Registers: W x (2 + 1 + 2) for the sums
 // and W for the row, 96 of them at W = 16.
-template <typename K, int W>
+//
+// What the workgroup walks is its source's to say -- where the list begins inside the gene's segment, its k stored kept
+// entries and the m cells they are ranked among: the gene's whole list (cna_gene_rank_corr) or, behind the sort's pass on
+// the level, the sub-segment of level blockIdx.y (cna_gene_rank_corr_by: k_l, m_l, z_l = m_l - k_l; a run cannot cross a
+// level because the list is one level's, and b sums to 0 over the level's kept cells, so the zero group's share holds).
+// Results go to [level][column][gene] and [level][gene].
+struct WholeGene {
+  const unsigned int* kept;
+  long long m;
+  __device__ __forceinline__ void operator()(int64_t g, int64_t, int, long long* at, long long* k, long long* cells) const {
+    *at = 0;
+    *k = (long long)kept[g];
+    *cells = m;
+  }
+};
+struct GeneLevel {
+  const unsigned int* dbase;          // [gene of the tile][digit] of the sort's last pass
+  const unsigned long long* mlev;     // kept cells per level
+  __device__ __forceinline__ void operator()(int64_t, int64_t in_tile, int level, long long* at, long long* k, long long* cells) const {
+    *at = (long long)dbase[in_tile * 256 + level];
+    *k = (long long)dbase[in_tile * 256 + level + 1] - *at;
+    *cells = (long long)mlev[level];
+  }
+};
+
+template <typename K, int W, class Src>
 __global__ __launch_bounds__(RS_UNIT) void k_rc_corr(const K* __restrict__ key, const uint32_t* __restrict__ cell,
                                                      const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,
-                                                     const unsigned int* __restrict__ kept, int64_t n, long long m, int q,
+                                                     Src src, int64_t n, int q,
                                                      const BRow<W>* __restrict__ btab, unsigned long long* __restrict__ s_lo,
                                                      long long* __restrict__ s_hi, double* __restrict__ tie) {
   constexpr K K0 = (K)1 << (8 * sizeof(K) - 1);       // the key of +0.0
@@ -726,9 +819,14 @@ __global__ __launch_bounds__(RS_UNIT) void k_rc_corr(const K* __restrict__ key, 
   __shared__ unsigned int below, zeros;
   const int t = threadIdx.x;
   const int64_t g = g0 + blockIdx.x;
-  const long long k = (long long)kept[g], z = m - k;
-  key += seg[g] - base;
-  cell += seg[g] - base;
+  long long at, k, m;
+  src(g, (int64_t)blockIdx.x, (int)blockIdx.y, &at, &k, &m);
+  const long long z = m - k;
+  key += seg[g] - base + at;
+  cell += seg[g] - base + at;
+  s_lo += (int64_t)blockIdx.y * q * G;
+  s_hi += (int64_t)blockIdx.y * q * G;
+  tie += (int64_t)blockIdx.y * G;
   if (t == 0) below = zeros = 0;
   __syncthreads();
   unsigned long long lo[W];
@@ -872,21 +970,30 @@ int dense_table(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t len, int64_t s
 }
 
 // The radix passes over the chunks [c0, c0 + nch) of the segments [g0, g0 + genes) of a table, whose entries begin at
-// `base`: an even number of passes, so the sorted {key, payload} are in (ka, pa) again
+// `base`: an even number of value passes, so the sorted {key, payload} are in (ka, pa) again.  With `lvl8` (the payload is
+// the cell) one more stable pass on the level of the entry's cell: every segment is then level-major and sorted by value
+// inside a level, in (kb, pb), the entries of the left-out cells last, and dbase[segment - g0][l] is where level l begins
+// inside the segment (so dbase[..][l + 1] is where it ends: l <= 254)
+template <typename K, typename P, class D>
+void rs_pass(hipStream_t st, const SortTable& tb, int64_t c0, int64_t nch, int64_t g0, unsigned genes, int64_t base, const K* ka,
+             const P* pa, K* kb, P* pb, D digit, unsigned int* cnt, unsigned int* dbase) {
+  hipLaunchKernelGGL((k_rs_count<K, P, D>), dim3((unsigned)nch), dim3(256), 0, st, tb.chunk_lo, tb.chunk_gene, tb.seg, c0,
+                     tb.chunk_len, base, ka, pa, digit, cnt);
+  hipLaunchKernelGGL(k_rs_scan, dim3(genes), dim3(256), 0, st, tb.gchunk, g0, c0, cnt, dbase);
+  hipLaunchKernelGGL((k_rs_scatter<K, P, D>), dim3((unsigned)nch), dim3(64), 0, st, tb.chunk_lo, tb.chunk_gene, tb.seg, c0,
+                     tb.chunk_len, base, g0, ka, pa, kb, pb, digit, (const unsigned int*)cnt, (const unsigned int*)dbase);
+}
 template <typename K, typename P>
 void rs_passes(hipStream_t st, const SortTable& tb, int64_t c0, int64_t nch, int64_t g0, unsigned genes, int64_t base, K* ka,
-               P* pa, K* kb, P* pb, unsigned int* cnt, unsigned int* dbase) {
-  static_assert(sizeof(K) % 2 == 0, "the result is to land where the keys were");
+               P* pa, K* kb, P* pb, unsigned int* cnt, unsigned int* dbase, const uint8_t* lvl8 = nullptr) {
+  static_assert(sizeof(K) % 2 == 0, "the result of the value passes is to land where the keys were");
   for (int pass = 0; pass < (int)sizeof(K); ++pass) {
-    const int shift = 8 * pass;
-    hipLaunchKernelGGL(k_rs_count<K>, dim3((unsigned)nch), dim3(256), 0, st, tb.chunk_lo, tb.chunk_gene, tb.seg, c0,
-                       tb.chunk_len, base, (const K*)ka, shift, cnt);
-    hipLaunchKernelGGL(k_rs_scan, dim3(genes), dim3(256), 0, st, tb.gchunk, g0, c0, cnt, dbase);
-    hipLaunchKernelGGL((k_rs_scatter<K, P>), dim3((unsigned)nch), dim3(64), 0, st, tb.chunk_lo, tb.chunk_gene, tb.seg, c0,
-                       tb.chunk_len, base, g0, (const K*)ka, (const P*)pa, kb, pb, shift, (const unsigned int*)cnt,
-                       (const unsigned int*)dbase);
+    rs_pass(st, tb, c0, nch, g0, genes, base, (const K*)ka, (const P*)pa, kb, pb, DigitOfKey<K, P>{8 * pass}, cnt, dbase);
     std::swap(ka, kb);
     std::swap(pa, pb);
+  }
+  if constexpr (sizeof(P) == 4) {
+    if (lvl8) rs_pass(st, tb, c0, nch, g0, genes, base, (const K*)ka, (const P*)pa, kb, pb, DigitOfLevel<K, P>{lvl8}, cnt, dbase);
   }
 }
 
@@ -904,9 +1011,11 @@ int rs_sort_bufs(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t entries, int6
 
 // Tiling, keys and the radix passes of the resident matrix, shared by the entry points: for every tile of whole genes
 // `behind(tile, base, keys, payloads, seg)` queues the kernel that reads the tile's sorted lists.  P: what an entry carries
-// (rs_payload); the cells with codes[i] >= 0 (w->sort.code) are kept.  `who` names the entry in what is refused.
+// (rs_payload); the cells with codes[i] >= 0 (w->sort.code) are kept.  `who` names the entry in what is refused.  With `lvl8`
+// the lists are level-major (rs_passes) and w->dbase holds, per gene of the tile, where each level begins.
 template <typename T, typename P, class Behind>
-int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes, int64_t m, const char* who, Behind&& behind) {
+int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes, int64_t m, const char* who, Behind&& behind,
+                   const uint8_t* lvl8 = nullptr) {
   using K = typename KeyOf<T>::K;
   const int64_t n = s->n, G = s->G;
   const bool dense = s->format == 1;
@@ -966,9 +1075,12 @@ int ranksum_sorted(cna_ctx* c, ExprState* s, RankSumWork* w, int64_t work_bytes,
                              base, ka, la, w->kept.as<unsigned int>(), w->nanf.as<unsigned int>());
       }
       ProfScope ps(c, CNA_K_RANKSUM_SORT, s->st);
-      rs_passes<K, P>(s->st, tb, t.c0, t.nch, t.g0, genes, base, ka, la, kb, lb, cnt, dbase);
+      rs_passes<K, P>(s->st, tb, t.c0, t.nch, t.g0, genes, base, ka, la, kb, lb, cnt, dbase, lvl8);
+    } else if (lvl8) {
+      HIP_TRY(hipMemsetAsync(dbase, 0, (size_t)(4 * 256) * genes, s->st));   // no entry, no pass: every level is empty
     }
-    behind(t, base, (const K*)ka, (const P*)la, tb.seg);
+    if (lvl8) behind(t, base, (const K*)kb, (const P*)lb, tb.seg);           // an odd number of passes: the other buffers
+    else behind(t, base, (const K*)ka, (const P*)la, tb.seg);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1004,19 +1116,23 @@ int pairs_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int n_pairs,
 }
 
 // The columns' ranks: tiles of whole columns within the budget, each a segment of n entries in a table of the dense form's
-// shape; sorted by the same passes, then k_rc_keyrank writes btab and the tie terms
-int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, int64_t work_bytes, int64_t m) {
+// shape; sorted by the same passes, then k_rc_keyrank writes btab and the tie terms.  With `lvl8` (cna_gene_rank_corr_by)
+// the passes end on the level and the ranks are those inside it.
+int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, int64_t work_bytes, int64_t m, int n_bins,
+                  const uint8_t* lvl8, const char* who) {
   const int64_t n = s->n, per = (n + RS_DENSE_CHUNK - 1) / RS_DENSE_CHUNK;
   const int64_t per_entry = 2 * (int64_t)(sizeof(uint64_t) + sizeof(uint32_t));
   const int64_t max_entries = std::max<int64_t>(1, (work_bytes > 0 ? work_bytes : RS_WORK_BYTES) / per_entry);
   const int cols = (int)std::min<int64_t>(q, std::max<int64_t>(1, max_entries / n));
-  if (cols * per > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: more than 2^31 - 1 chunks in one tile of columns");
+  if (cols * per > 0x7fffffffll) CNA_FAIL(CNA_EINVAL, std::string(who) + ": more than 2^31 - 1 chunks in one tile of columns");
   std::vector<int64_t> seg_h, gchunk_h;
   SortTable tb;
   CNA_TRY(dense_table(c, s, w, n, q, seg_h, gchunk_h, &tb));
   CNA_TRY((rs_sort_bufs<uint64_t, uint32_t>(c, s, w, cols * n, cols * per, cols)));
   uint64_t *ka = w->keyA.as<uint64_t>(), *kb = w->keyB.as<uint64_t>();
   uint32_t *pa = w->lvlA.as<uint32_t>(), *pb = w->lvlB.as<uint32_t>();
+  unsigned long long* tie_lo = w->tiek.as<unsigned long long>();
+  unsigned int* tie_hi = w->tiek.as<unsigned int>() + 2 * RC_MAX_KEYS * n_bins;
   for (int k0 = 0; k0 < q; k0 += cols) {
     const int k1 = std::min(q, k0 + cols);
     {
@@ -1027,36 +1143,119 @@ int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, i
     {
       ProfScope ps(c, CNA_K_RANKSUM_SORT, s->st);
       rs_passes<uint64_t, uint32_t>(s->st, tb, k0 * per, (k1 - k0) * per, k0, (unsigned)(k1 - k0), k0 * n, ka, pa, kb, pb,
-                                    w->cnt.as<unsigned int>(), w->dbase.as<unsigned int>());
+                                    w->cnt.as<unsigned int>(), w->dbase.as<unsigned int>(), lvl8);
     }
     ProfScope ps(c, CNA_K_RANKCORR_KEYS, s->st);
-    if (m > 0)
-      hipLaunchKernelGGL(k_rc_keyrank, dim3((unsigned)((m + 255) / 256), (unsigned)(k1 - k0)), dim3(256), 0, s->st,
-                         (const uint64_t*)ka, (const uint32_t*)pa, n, k0, (long long)m, stride, w->btab.as<int32_t>(),
-                         w->tiek.as<unsigned long long>(), w->tiek.as<unsigned int>() + 2 * RC_MAX_KEYS);
+    const dim3 grid((unsigned)((m + 255) / 256), (unsigned)(k1 - k0));
+    if (m > 0 && lvl8)
+      hipLaunchKernelGGL(k_rc_keyrank<true>, grid, dim3(256), 0, s->st, (const uint64_t*)kb, (const uint32_t*)pb, n, k0,
+                         (long long)m, stride, w->btab.as<int32_t>(), tie_lo, tie_hi, lvl8, w->dbase.as<const unsigned int>());
+    else if (m > 0)
+      hipLaunchKernelGGL(k_rc_keyrank<false>, grid, dim3(256), 0, s->st, (const uint64_t*)ka, (const uint32_t*)pa, n, k0,
+                         (long long)m, stride, w->btab.as<int32_t>(), tie_lo, tie_hi, (const uint8_t*)nullptr,
+                         (const unsigned int*)nullptr);
   }
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
 template <typename T>
-int rankcorr_run(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int64_t work_bytes, int64_t m) {
+int rankcorr_run(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int64_t work_bytes, int64_t m, int n_bins, const uint8_t* lvl8,
+                 const char* who) {
   using K = typename KeyOf<T>::K;
   const int64_t G = s->G, n = s->n;
   int rc = 0;
   with_width(q, [&](auto width) {
     constexpr int W = decltype(width)::value;
-    rc = ranksum_sorted<T, uint32_t>(c, s, w, work_bytes, m, "cna_gene_rank_corr",
-                                     [&](const GeneTile& t, int64_t base, const K* key, const uint32_t* cell, const int64_t* seg) {
-                                       ProfScope ps(c, CNA_K_RANKCORR_CORR, s->st);
-                                       hipLaunchKernelGGL((k_rc_corr<K, W>), dim3((unsigned)(t.g1 - t.g0)), dim3(RS_UNIT), 0, s->st,
-                                                          key, cell, seg, base, t.g0, G, w->kept.as<const unsigned int>(), n,
-                                                          (long long)m, q, w->btab.as<const BRow<W>>(),
-                                                          w->slo.as<unsigned long long>(), w->shi.as<long long>(),
-                                                          w->tie.as<double>());
-                                     });
+    rc = ranksum_sorted<T, uint32_t>(
+        c, s, w, work_bytes, m, who,
+        [&](const GeneTile& t, int64_t base, const K* key, const uint32_t* cell, const int64_t* seg) {
+          ProfScope ps(c, CNA_K_RANKCORR_CORR, s->st);
+          const dim3 grid((unsigned)(t.g1 - t.g0), (unsigned)n_bins);
+          if (lvl8)
+            hipLaunchKernelGGL((k_rc_corr<K, W, GeneLevel>), grid, dim3(RS_UNIT), 0, s->st, key, cell, seg, base, t.g0, G,
+                               GeneLevel{w->dbase.as<const unsigned int>(), w->vm.as<const unsigned long long>()}, n, q,
+                               w->btab.as<const BRow<W>>(), w->slo.as<unsigned long long>(), w->shi.as<long long>(),
+                               w->tie.as<double>());
+          else
+            hipLaunchKernelGGL((k_rc_corr<K, W, WholeGene>), grid, dim3(RS_UNIT), 0, s->st, key, cell, seg, base, t.g0, G,
+                               WholeGene{w->kept.as<const unsigned int>(), (long long)m}, n, q, w->btab.as<const BRow<W>>(),
+                               w->slo.as<unsigned long long>(), w->shi.as<long long>(), w->tie.as<double>());
+        },
+        lvl8);
   });
   return rc;
+}
+
+// What cna_gene_rank_corr and cna_gene_rank_corr_by share behind their argument checks.  `codes` null: one level of all
+// cells (n_bins = 1), the whole-gene kernels, bit for bit the entry as it was; else the levels, judged before anything is
+// written.  Outputs per level: s_lo, s_hi [n_bins, q, G], tie_gene [n_bins, G], tie_key [n_bins, q], m_out [n_bins].
+int rankcorr_entry(cna_ctx* c, ExprState* s, const char* who, const double* V, int q, const int32_t* codes, int n_bins,
+                   int64_t work_bytes, uint64_t* s_lo, int64_t* s_hi, double* tie_gene, double* tie_key, int64_t* m_out,
+                   uint8_t* nan_out) {
+  const int64_t G = s->G, n = s->n;
+  const bool by = codes != nullptr;
+  int stride = 1;
+  with_width(q, [&](auto width) { stride = decltype(width)::value; });
+  RankSumWork* w = expr_work<RankSumWork>(s, EXPR_RANKSUM);
+  if (by) CNA_TRY(sort_count(c, s->st, w->sort, CellListOf<256>{}, codes, n, n_bins, 0, 2,
+                             (std::string(who) + ": a code lies outside [-1, n_bins)").c_str()));
+  const int64_t tie_bytes = 12 * RC_MAX_KEYS * (int64_t)n_bins;   // per (level, column) 64 low bits, then 32 high bits, of its tie term
+  CNA_TRY(buf_need(c, s->st, w->vcol, 8 * (int64_t)q * n));
+  CNA_TRY(buf_need(c, s->st, w->sort.code, 4 * n));
+  CNA_TRY(buf_need(c, s->st, w->vm, 8 * 256));
+  CNA_TRY(buf_need(c, s->st, w->btab, 4 * (int64_t)stride * n));
+  CNA_TRY(buf_need(c, s->st, w->tiek, tie_bytes));
+  if (by) CNA_TRY(buf_need(c, s->st, w->lvl8, n));
+  for (Buf* b : {&w->slo, &w->shi, &w->tie}) {
+    const int rc = buf_need(c, s->st, *b, 8 * (int64_t)n_bins * (b == &w->tie ? 1 : q) * G);
+    if (rc == CNA_ENOMEM) (void)hipGetLastError();    // the refusal is the caller's to see, not the next launch's
+    CNA_TRY(rc);
+  }
+  const uint8_t* lvl8 = by ? w->lvl8.as<const uint8_t>() : nullptr;
+  std::vector<unsigned long long> mlev((size_t)n_bins);
+  {
+    // the kept cells: every column finite.  The rows of btab of the other cells, and its columns from q on, are never
+    // meant: zero, so that what the gather reads of them is defined
+    ProfScope ps(c, CNA_K_RANKCORR_KEYS, s->st);
+    HIP_TRY(hipMemcpyAsync(w->vcol.p, V, (size_t)(8 * (int64_t)q * n), hipMemcpyHostToDevice, s->st));
+    HIP_TRY(hipMemsetAsync(w->vm.p, 0, 8 * 256, s->st));
+    HIP_TRY(hipMemsetAsync(w->tiek.p, 0, (size_t)tie_bytes, s->st));
+    HIP_TRY(hipMemsetAsync(w->btab.p, 0, (size_t)(4 * (int64_t)stride * n), s->st));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (by)
+      hipLaunchKernelGGL(k_rc_mask<true>, grid, dim3(256), 0, s->st, w->vcol.as<const double>(), q, n, w->sort.code.as<int32_t>(),
+                         w->lvl8.as<uint8_t>(), w->vm.as<unsigned long long>());
+    else
+      hipLaunchKernelGGL(k_rc_mask<false>, grid, dim3(256), 0, s->st, w->vcol.as<const double>(), q, n,
+                         w->sort.code.as<int32_t>(), (uint8_t*)nullptr, w->vm.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(mlev.data(), w->vm.p, 8 * (size_t)n_bins, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));             // the caller has its columns back
+  }
+  int64_t m = 0;
+  for (int b = 0; b < n_bins; ++b) m += (int64_t)mlev[(size_t)b];
+  CNA_TRY(rankcorr_keys(c, s, w, q, stride, work_bytes, m, n_bins, lvl8, who));
+  if (s->is_f64) CNA_TRY(rankcorr_run<double>(c, s, w, q, work_bytes, m, n_bins, lvl8, who));
+  else CNA_TRY(rankcorr_run<float>(c, s, w, q, work_bytes, m, n_bins, lvl8, who));
+  std::vector<unsigned int> nanf((size_t)G);
+  std::vector<unsigned long long> tie_words((size_t)(tie_bytes / 8));
+  {
+    ProfScope ps(c, CNA_K_RANKSUM_FETCH, s->st);
+    CNA_TRY(fetch_results(s->st, who, {{s_lo, w->slo.p, (size_t)(8 * (int64_t)n_bins * q * G)},
+                                       {s_hi, w->shi.p, (size_t)(8 * (int64_t)n_bins * q * G)},
+                                       {tie_gene, w->tie.p, (size_t)(8 * (int64_t)n_bins * G)},
+                                       {tie_words.data(), w->tiek.p, (size_t)tie_bytes},
+                                       {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
+  }
+  for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
+  const unsigned int* tie_high = reinterpret_cast<const unsigned int*>(tie_words.data() + RC_MAX_KEYS * n_bins);
+  for (int b = 0; b < n_bins; ++b) {
+    for (int k = 0; k < q; ++k)                       // rounded once
+      tie_key[b * q + k] = (double)tie_high[b * RC_MAX_KEYS + k] * 18446744073709551616.0 + (double)tie_words[(size_t)(b * RC_MAX_KEYS + k)];
+    m_out[b] = (int64_t)mlev[(size_t)b];
+  }
+  return 0;
 }
 
 }  // namespace
@@ -1142,50 +1341,19 @@ extern "C" int cna_gene_rank_corr(cna_ctx* c, const double* V, int q, int64_t wo
   if (!V || !s_lo || !s_hi || !tie_gene || !tie_key || !m_out || !nan_out) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: null pointer");
   if (q < 1 || q > RC_MAX_KEYS) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: 1 <= q <= 16");
   if (work_bytes < 0) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr: work_bytes is 0 (the default) or a number of bytes");
-  const int64_t G = s->G, n = s->n;
-  int stride = 1;
-  with_width(q, [&](auto width) { stride = decltype(width)::value; });
-  RankSumWork* w = expr_work<RankSumWork>(s, EXPR_RANKSUM);
-  CNA_TRY(buf_need(c, s->st, w->vcol, 8 * (int64_t)q * n));
-  CNA_TRY(buf_need(c, s->st, w->sort.code, 4 * n));
-  CNA_TRY(buf_need(c, s->st, w->vm, 8));
-  CNA_TRY(buf_need(c, s->st, w->btab, 4 * (int64_t)stride * n));
-  CNA_TRY(buf_need(c, s->st, w->tiek, 12 * RC_MAX_KEYS));   // per column 64 low bits, then 32 high bits, of its tie term
-  CNA_TRY(buf_need(c, s->st, w->slo, 8 * (int64_t)q * G));
-  CNA_TRY(buf_need(c, s->st, w->shi, 8 * (int64_t)q * G));
-  CNA_TRY(buf_need(c, s->st, w->tie, 8 * G));
-  unsigned long long m_dev = 0;
-  {
-    // the kept cells: every column finite.  The rows of btab of the other cells, and its columns from q on, are never
-    // meant: zero, so that what the gather reads of them is defined
-    ProfScope ps(c, CNA_K_RANKCORR_KEYS, s->st);
-    HIP_TRY(hipMemcpyAsync(w->vcol.p, V, (size_t)(8 * (int64_t)q * n), hipMemcpyHostToDevice, s->st));
-    HIP_TRY(hipMemsetAsync(w->vm.p, 0, 8, s->st));
-    HIP_TRY(hipMemsetAsync(w->tiek.p, 0, 12 * RC_MAX_KEYS, s->st));
-    HIP_TRY(hipMemsetAsync(w->btab.p, 0, (size_t)(4 * (int64_t)stride * n), s->st));
-    hipLaunchKernelGGL(k_rc_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, w->vcol.as<const double>(), q, n,
-                       w->sort.code.as<int32_t>(), w->vm.as<unsigned long long>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&m_dev, w->vm.p, 8, hipMemcpyDeviceToHost, s->st));
-    HIP_TRY(hipStreamSynchronize(s->st));             // the caller has its columns back
-  }
-  const int64_t m = (int64_t)m_dev;
-  CNA_TRY(rankcorr_keys(c, s, w, q, stride, work_bytes, m));
-  if (s->is_f64) CNA_TRY(rankcorr_run<double>(c, s, w, q, work_bytes, m));
-  else CNA_TRY(rankcorr_run<float>(c, s, w, q, work_bytes, m));
-  std::vector<unsigned int> nanf((size_t)G);
-  unsigned long long tie_words[RC_MAX_KEYS + RC_MAX_KEYS / 2];
-  {
-    ProfScope ps(c, CNA_K_RANKSUM_FETCH, s->st);
-    CNA_TRY(fetch_results(s->st, "cna_gene_rank_corr", {{s_lo, w->slo.p, (size_t)(8 * (int64_t)q * G)},
-                                                       {s_hi, w->shi.p, (size_t)(8 * (int64_t)q * G)},
-                                                       {tie_gene, w->tie.p, (size_t)(8 * G)},
-                                                       {tie_words, w->tiek.p, sizeof(tie_words)},
-                                                       {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
-  }
-  for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
-  const unsigned int* tie_high = reinterpret_cast<const unsigned int*>(tie_words + RC_MAX_KEYS);
-  for (int k = 0; k < q; ++k) tie_key[k] = (double)tie_high[k] * 18446744073709551616.0 + (double)tie_words[k];   // rounded once
-  *m_out = m;
-  return 0;
+  return rankcorr_entry(c, s, "cna_gene_rank_corr", V, q, nullptr, 1, work_bytes, s_lo, s_hi, tie_gene, tie_key, m_out, nan_out);
+}
+
+extern "C" int cna_gene_rank_corr_by(cna_ctx* c, const double* V, int q, const int32_t* codes, int n_bins, int64_t work_bytes,
+                                     uint64_t* s_lo, int64_t* s_hi, double* tie_gene, double* tie_key, int64_t* m_out,
+                                     uint8_t* nan_out) {
+  CHECK_CTX(c);
+  ExprState* s = expr_state(c);
+  if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_gene_rank_corr_by: no expression matrix is resident (cna_expr_upload_*)");
+  if (!V || !codes || !s_lo || !s_hi || !tie_gene || !tie_key || !m_out || !nan_out)
+    CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr_by: null pointer");
+  if (q < 1 || q > RC_MAX_KEYS) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr_by: 1 <= q <= 16");
+  if (n_bins < 1 || n_bins > RC_MAX_LEVELS) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr_by: 1 <= n_bins <= 255");
+  if (work_bytes < 0) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr_by: work_bytes is 0 (the default) or a number of bytes");
+  return rankcorr_entry(c, s, "cna_gene_rank_corr_by", V, q, codes, n_bins, work_bytes, s_lo, s_hi, tie_gene, tie_key, m_out, nan_out);
 }

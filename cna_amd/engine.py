@@ -1390,6 +1390,30 @@ class Engine(_order.CellOrder):
                                           C.byref(m), ptr(nan)), 'cna_gene_rank_corr')
         return s_lo, s_hi, tie_gene, tie_key, int(m.value), nan.astype(bool)
 
+    def gene_rank_corr_by(self, V, codes, n_levels, work_bytes=0):
+        """The integers of `gene_rank_corr` inside every level of `codes` (int32 per cell, -1 = cell left out, at most 255
+        levels) from one sort of the matrix (cna_gene_rank_corr_by): level l is ranked over its cells where every row of V
+        is finite, m[l] of them.  Returns (s_lo uint64[L, q, genes], s_hi int64[L, q, genes], tie_gene float64[L, genes],
+        tie_key float64[L, q], m int64[L], nan bool[genes]: a kept cell of any level holds NaN and the gene's numbers mean
+        nothing); level l's slices are what `gene_rank_corr` returns for V set to NaN outside the level."""
+        V = _f64(V)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        info = self.expression_shape()
+        if info['format'] != 'none' and (V.ndim != 2 or V.shape[1] != info['n_cells'] or codes.shape != (info['n_cells'],)):
+            raise ValueError('gene_rank_corr_by: keys %s and %d codes for %d resident cells'
+                             % (V.shape, codes.size, info['n_cells']))
+        q = int(V.shape[0]) if V.ndim == 2 else 0
+        L, G = max(int(n_levels), 0), info['n_genes']
+        s_lo = np.empty((L, max(q, 0), G), dtype=np.uint64)
+        s_hi = np.empty((L, max(q, 0), G), dtype=np.int64)
+        tie_gene = np.empty((L, G))
+        tie_key = np.empty((L, max(q, 0)))
+        m = np.empty(L, dtype=np.int64)
+        nan = np.empty(G, dtype=np.uint8)
+        check(self.lib.cna_gene_rank_corr_by(self.h, ptr(V), q, ptr(codes), int(n_levels), int(work_bytes), ptr(s_lo), ptr(s_hi),
+                                             ptr(tie_gene), ptr(tie_key), ptr(m), ptr(nan)), 'cna_gene_rank_corr_by')
+        return s_lo, s_hi, tie_gene, tie_key, m, nan.astype(bool)
+
     BW_KINDS = ('scott', 'silverman', 'constant')
 
     def coef_strata(self, v, fdr, codes, n_bins, fdr_thresh, points, bw_kind='scott', bw_value=0.0):

@@ -9,7 +9,7 @@ from ._populations import coef_populations
 from ._gene_strata import gene_corr_strata
 from ._gene_test_strata import gene_test_strata
 from ._gene_markers import gene_markers, gene_markers_pairs
-from ._gene_rank_corr import gene_rank_corr
+from ._gene_rank_corr import gene_rank_corr, gene_rank_corr_strata
 from ._nam_strata import nam_strata
 from ._gene_sets import gene_set_enrich, gene_set_test
 
@@ -23,6 +23,7 @@ __all__ = [
     'gene_markers',
     'gene_markers_pairs',
     'gene_rank_corr',
+    'gene_rank_corr_strata',
     'gene_set_enrich',
     'gene_set_test',
     'gene_test',

@@ -15,6 +15,9 @@ import pandas as pd
 from ..engine import get_engine
 from ._genes import expression_of, gene_index, key_columns
 from ._nam import refuse_sharded
+from ._strata import levels_of
+
+MAX_LEVELS = 255        # cna_gene_rank_corr_by: the level is one digit of the sort, 255 stands for a left-out entry
 
 
 def wide_to_float(s_lo, s_hi):
@@ -75,7 +78,7 @@ def gene_rank_corr(data, keys='coef', layer=None, key_added=None, engine=None):
     prefix) also writes ``data.var[key_added + key]``.
 
     Not here: p-values (cells are not independent, so the t approximation would be anti-conservative: ``gene_test`` is
-    the answer to that, and a rank version of it is not built), rank correlation within strata, Kendall's tau, gene-gene
+    the answer to that, and a rank version of it is not built), Kendall's tau, gene-gene
     rank correlations, a kept set per key, more than 16 keys per call, sharded data."""
     engine = engine or get_engine()
     refuse_sharded(data, engine, 'gene_rank_corr', 'the ranking runs over all cells of a gene: the rows of other ranks are elsewhere')
@@ -93,3 +96,58 @@ def gene_rank_corr(data, keys='coef', layer=None, key_added=None, engine=None):
         for k in names:
             data.var['%s%s' % (key_added, k)] = out[k].values
     return out
+
+
+def gene_rank_corr_strata(data, stratification, keys='coef', layer=None, engine=None):
+    """Spearman's rank correlation of every gene with one or several numeric columns of ``data.obs`` (1 to 16, as in
+    ``gene_rank_corr``) inside each distinct value of ``data.obs[stratification]`` (levels in order of first appearance, as
+    ``gene_corr_strata`` orders them): which genes separate the expanded from the depleted cells inside a cluster, or
+    inside a ``coef_populations`` population.  A cluster has few cells, its counts are zero-inflated and its coefficient is
+    smooth, so a handful of cells easily carries ``gene_corr_strata``'s Pearson r, and that r moves with whatever
+    normalisation ``X`` went through; the rank version does neither.
+
+    Kept cells: ``C_l``, the cells of level ``l`` where EVERY key of the call is finite -- ``gene_rank_corr``'s one kept set
+    per call, intersected with the level; cells whose level is NaN / None are in no level.  ``m_l`` is their number,
+    ``frame.attrs['n_cells']`` (a Series indexed by level).
+
+    Ranks: genes and keys are both ranked with midranks over ``C_l``, under ``gene_rank_corr``'s rules (``-0.0`` = ``+0.0``
+    = a stored zero = an implicit zero, float64 on all 64 bits, ``+-inf`` ordinary values of a gene).
+
+    NaN results: a gene that is constant on ``C_l`` (a sparse gene with no stored entry in the level among them), a key
+    that is constant on ``C_l``, ``m_l < 2``; and a gene with a NaN in a kept cell of ANY level, in every level -- a guard
+    on the whole gene, as in ``gene_rank_corr``, not what scipy would say level by level.  Where nothing is NaN the result
+    is ``scipy.stats.spearmanr(x_g[C_l], v_k[C_l]).statistic``.
+
+    The matrix is ``data.X`` or ``data.layers[layer]``, resident on the device and shared with the other gene tools.  All
+    levels come from one sort of the matrix (``cna_gene_rank_corr_by``: one more radix pass on the level behind the value
+    passes), as integers; rho is ``rank_corr_statistics`` on each level's integers.
+
+    Returns a float64 DataFrame indexed by ``data.var_names`` (a ``RangeIndex`` when there are none); its columns are the
+    levels (an Index named after the stratification) for a ``str`` key, a MultiIndex ``(key, level)``, key-major, for a
+    list of keys.
+
+    Not here: p-values (as in ``gene_rank_corr``), a pooled "within" coefficient across the levels (ranks inside different
+    levels do not pool the way ``gene_corr_strata``'s centred sums do), more than 255 levels or 16 keys per call, sharded
+    data."""
+    engine = engine or get_engine()
+    refuse_sharded(data, engine, 'gene_rank_corr_strata',
+                   'the ranking runs over all cells of a level: the rows of other ranks are elsewhere')
+    obs = data.obs
+    if stratification not in obs:
+        raise KeyError(stratification)
+    names, V = key_columns(obs, keys)
+    codes, levels = levels_of(obs, stratification, 'gene_rank_corr_strata', max_levels=MAX_LEVELS)
+    X = expression_of(data, layer, 'gene_rank_corr_strata')
+    engine.ensure_expression(X)
+    s_lo, s_hi, tie_gene, tie_key, m, nan = engine.gene_rank_corr_by(V, codes, len(levels))
+    rho = np.stack([rank_corr_statistics(s_lo[l], s_hi[l], tie_gene[l], tie_key[l], int(m[l]), nan)
+                    for l in range(len(levels))], axis=1)                     # [key, level, gene]
+    index = gene_index(data, X.shape[1])
+    level_index = pd.Index(levels, name=stratification)
+    if isinstance(keys, str):
+        frame = pd.DataFrame(rho[0].T, index=index, columns=level_index)
+    else:
+        columns = pd.MultiIndex.from_product([names, level_index], names=['key', stratification])
+        frame = pd.DataFrame(rho.reshape(len(names) * len(levels), -1).T, index=index, columns=columns)
+    frame.attrs['n_cells'] = pd.Series(np.asarray(m, dtype=np.int64), index=level_index)
+    return frame

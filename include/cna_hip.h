@@ -635,7 +635,7 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
  * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster, cna_graph_components_find,
- * cna_gene_ranksum_by, cna_gene_ranksum_pairs and cna_gene_rank_corr: cna_ctx_device_bytes returns to what it was before the upload. */
+ * cna_gene_ranksum_by, cna_gene_ranksum_pairs, cna_gene_rank_corr and cna_gene_rank_corr_by: cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -814,6 +814,33 @@ int  cna_gene_ranksum_pairs(cna_ctx* ctx, const int32_t* codes, int n_bins, cons
  * a negative work_bytes. */
 int  cna_gene_rank_corr(cna_ctx* ctx, const double* V, int q, int64_t work_bytes, uint64_t* s_lo_out, int64_t* s_hi_out,
                         double* tie_gene_out, double* tie_key_out, int64_t* m_out, uint8_t* nan_out);
+
+/* The same inside every level of a clustering (cna.tl.gene_rank_corr_strata): for level l, column k and gene g the integers
+ * of scipy.stats.spearmanr(x_g[C_l], v_k[C_l]), where C_l holds the cells of level l in which EVERY column of the call is
+ * finite -- cna_gene_rank_corr's one kept set per call, intersected with the level -- and genes and columns are ranked
+ * with midranks over C_l, under cna_gene_rank_corr's rules for ties and zeros.
+ *   codes[i]  the level of cell i in [0, n_bins), or -1: the cell is left out.  1 <= n_bins <= 255
+ *   s_lo_out, s_hi_out [(l * q + k) * n_genes + g]   S of level l: a and b are 2 x midrank - (m_l + 1), ranked inside C_l
+ *   tie_gene_out[l * n_genes + g], tie_key_out[l * q + k]   the tie terms inside C_l, formed as cna_gene_rank_corr's
+ *   m_out[l] = m_l = |C_l|
+ *   nan_out[g]  a cell of ANY C_l holds NaN in gene g: a guard on the whole gene (its other outputs are unspecified in
+ *             every level), not scipy's behaviour level by level
+ * so that rho of level l is rank_corr_statistics' line on the level's slices, NaN for a gene that is constant on C_l (a
+ * sparse gene with no stored entry there among them), a column that is constant on C_l and m_l < 2.  Level l equals
+ * cna_gene_rank_corr called with the columns set to NaN outside level l, integer for integer (s_lo, s_hi, both tie terms
+ * and m), from one sort of the matrix instead of one per level: behind the value passes one more stable radix pass takes
+ * the level of the entry's cell as its digit (255: a left-out entry), which leaves every gene's list, and every column's
+ * segment, level-major and sorted by value inside a level, the scan of that pass being the table of where each (gene,
+ * level) begins; the columns' ranks are searched inside the level's range, and one workgroup per (gene, level) runs
+ * cna_gene_rank_corr's walk on its sub-segment with m_l cells, k_l stored entries and m_l - k_l implicit zeros.
+ * work_bytes, the stream, the buffers and the states it may be called in: as cna_gene_rank_corr.  The same bits on every
+ * run, under every work_bytes and for a CSR and a CSC upload of one matrix.
+ * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL, with nothing written: a null pointer, q outside [1, 16],
+ * n_bins outside [1, 255], a negative work_bytes, a code outside [-1, n_bins).  CNA_ENOMEM: the results do not fit on
+ * the device. */
+int  cna_gene_rank_corr_by(cna_ctx* ctx, const double* V, int q, const int32_t* codes, int n_bins, int64_t work_bytes,
+                           uint64_t* s_lo_out, int64_t* s_hi_out, double* tie_gene_out, double* tie_key_out, int64_t* m_out,
+                           uint8_t* nan_out);
 
 /* ---- the expression matrix against the working matrix (csrc/expr_cross.hip) ------------------- */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
