@@ -4,17 +4,17 @@
 // (nam_bins.hip: the NAM or X by bin, on this stream with this sort), cna_enrichment_extremes (enrich.hip: no matrix at all,
 // this stream and these buffers), cna_expr_cross_by (expr_cross_by.hip), cna_gram_by (gram_by.hip: X alone) and
 // cna_coef_raster (raster.hip: no matrix, this stream, the sort twice); cna_graph_components_* (components.hip) borrows the
-// stream and a slot of buffers and reads the resident graph; cna_gene_ranksum_by (expr_ranksum.hip: a ranking of the cells
-// of every gene, with a radix sort of its own on the chunk tables), cna_gene_ranksum_pairs (the same file, sort and
-// buffers: level against level) and cna_gene_rank_corr (the same again: the sort with the cell as payload, Spearman's rho
-// against per-cell columns).  What two of them need is here once:
+// stream and a slot of buffers and reads the resident graph; cna_gene_ranksum_by and cna_gene_ranksum_pairs
+// (expr_ranksum.hip: rank sums from a ranking of the cells of every gene) and cna_gene_rank_corr and cna_gene_rank_corr_by
+// (expr_rankcorr.hip: Spearman's rho against per-cell columns from the same ranking), the two files sharing rank_sort.h: a
+// radix sort on the chunk tables, the walk over a sorted list and their buffers.  What two of them need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared
 //   ExprState       the resident matrix, the stream, and one slot of work buffers per entry point
 //   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins and cna_gene_corr_by, value
 //                   segments of cna_coef_strata): one count kernel, one fill kernel, one host half; CellListOf
 //   gene_tiles      the walk over tiles of whole genes of the gene-major kernels
 //   xrow_check      the verdict on a map cells -> rows of X (cna_expr_cross and the two entries by level)
-//   with_bool / with_width, fetch_results, finite_d, wave_min / wave_max
+//   with_bool / with_width, fetch_results, result_bufs_need, finite_d, wave_min / wave_max
 // Templates are instantiated where they are used; nothing here needs relocatable device code.
 #pragma once
 #include "common.h"
@@ -105,6 +105,13 @@ struct HostCopy {
   size_t bytes;
 };
 int fetch_results(hipStream_t st, const char* who, std::initializer_list<HostCopy> copies);
+// Result buffers whose size is the caller's to choose (outputs x genes): grown in turn; CNA_ENOMEM is the caller's to see,
+// not the next launch's -- the runtime's sticky error is cleared
+struct BufSize {
+  Buf* buf;
+  int64_t bytes;
+};
+int result_bufs_need(cna_ctx* c, hipStream_t st, std::initializer_list<BufSize> bufs);
 
 // The verdict on a map cells -> rows of X (xrow_dev: n entries on the device; expr_cross.hip, k_xc_check): CNA_EINVAL under
 // who's name for a value outside [-1, nx) or a row named twice, before any sum is formed; *m = the cells with a row

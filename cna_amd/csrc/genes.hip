@@ -284,6 +284,15 @@ int fetch_results(hipStream_t st, const char* who, std::initializer_list<HostCop
   return 0;
 }
 
+int result_bufs_need(cna_ctx* c, hipStream_t st, std::initializer_list<BufSize> bufs) {
+  for (const BufSize& b : bufs) {
+    const int rc = buf_need(c, st, *b.buf, b.bytes);
+    if (rc == CNA_ENOMEM) (void)hipGetLastError();
+    CNA_TRY(rc);
+  }
+  return 0;
+}
+
 int expr_get_state(cna_ctx* c, ExprState** out) {
   if (!c->expr) {
     ExprState* s = new ExprState();

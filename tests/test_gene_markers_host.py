@@ -3,8 +3,8 @@ with, integer for integer), its check against scipy.stats.mannwhitneyu on the GP
 an engine double (GeneEngine of test_gene_corr_host.py with `gene_ranksum_by` backed by the restatement), and the proofs,
 without a device, that the GPU inputs reach what they are meant to reach: three sort chunks per long gene, two tiles of
 genes under the small budget, a tie run that ends on a cut of the rank kernel's unit and one that spans two cuts.  The
-constants of csrc/expr_ranksum.hip are read from the source, so a change there fails these proofs instead of leaving a path
-untested."""
+constants of csrc/rank_sort.h (the sort and the walk), csrc/expr_ranksum.hip and csrc/expr_rankcorr.hip are read from the
+source, so a change there fails these proofs instead of leaving a path untested."""
 import functools
 import os
 import re
@@ -24,8 +24,12 @@ Z_MAX = 30.0            # |z| of every checked (gene, level): the project's 1e-1
 P_RTOL = 1e-6           # ... relative, with a factor 10 of margin
 
 
+def ranksum_source(*files):
+    return ''.join(open(os.path.join(ROOT, 'cna_amd', 'csrc', f)).read() for f in files)
+
+
 def ranksum_constant(name):
-    src = open(os.path.join(ROOT, 'cna_amd', 'csrc', 'expr_ranksum.hip')).read()
+    src = ranksum_source('rank_sort.h', 'expr_ranksum.hip', 'expr_rankcorr.hip')
     m = re.search(r'constexpr (?:int|int64_t) %s = (\d+)(?:ll)?(?: << (\d+))?;' % name, src)
     assert m, name
     return int(m.group(1)) << int(m.group(2) or 0)

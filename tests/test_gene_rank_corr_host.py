@@ -3,8 +3,8 @@ with, integer for integer), its check against scipy.stats.spearmanr on the GPU t
 engine double (GeneEngine of test_gene_corr_host.py with `gene_rank_corr` backed by the restatement), and the proofs, without
 a device, that the GPU inputs reach what they are meant to reach: three sort chunks per long gene and per key, two tiles of
 genes and one tile per key under the small budget (recomputed for the 4-byte payload), tie runs of a gene and of a key that
-end on a cut of the kernels' unit and that span two, and a sum that passes 64 bits.  The constants of csrc/expr_ranksum.hip
-are read from the source."""
+end on a cut of the kernels' unit and that span two, and a sum that passes 64 bits.  The constants of csrc/rank_sort.h and
+csrc/expr_rankcorr.hip are read from the source."""
 import functools
 import os
 
@@ -16,7 +16,7 @@ import scipy.stats
 
 from test_gene_corr_host import GeneEngine, _frame
 from test_gene_markers_host import (FORMS, N_CORE, ROOT, RUN_ON_CUT, RUN_OVER_CUTS, SMALL_WORK_BYTES, _dense, core_codes,
-                                    core_input, core_values, markers_input, ranksum_constant, sort_chunks)
+                                    core_input, core_values, markers_input, ranksum_constant, ranksum_source, sort_chunks)
 
 RHO_TOL = 1e-10         # the project's figure for z in test_gene_markers_host.py
 WIDE_CELLS = 3100000    # the GPU tests' wide case
@@ -273,9 +273,8 @@ def rank_corr_tiles(form, work_bytes):
 
 @pytest.mark.parametrize('form', FORMS)
 def test_the_small_budget_cuts_at_least_two_tiles_of_genes_and_one_per_key(form):
-    src = open(os.path.join(ROOT, 'cna_amd', 'csrc', 'expr_ranksum.hip')).read()
-    assert 'per_entry = 2 * (int64_t)(sizeof(K) + sizeof(P))' in src
-    assert 'per_entry = 2 * (int64_t)(sizeof(uint64_t) + sizeof(uint32_t))' in src
+    assert 'per_entry = 2 * (int64_t)(sizeof(K) + sizeof(P))' in ranksum_source('rank_sort.h')       # ranksum_sorted
+    assert 'per_entry = 2 * (int64_t)(sizeof(uint64_t) + sizeof(uint32_t))' in ranksum_source('expr_rankcorr.hip')
     tiles, limit, length, cols = rank_corr_tiles(form, SMALL_WORK_BYTES)
     assert len(tiles) >= 2 and tiles[0][0] == 0 and tiles[-1][1] == 9 and cols == 1
     whole = rank_corr_tiles(form, 0)

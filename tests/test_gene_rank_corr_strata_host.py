@@ -4,8 +4,8 @@ against scipy.stats.spearmanr per (level, key, gene) on the GPU tests' own input
 and the proofs, without a device, that those inputs reach what they are meant to reach: inside ONE level a tie run of a gene
 and of a key that ends on a cut of the kernels' unit and one that spans two, a value shared by the last entry of a level and
 the first of the next, a (gene, level) without a stored entry, levels of 0, 1 and 2 kept cells, a level that loses cells to a
-non-finite key, two tiles of genes under the small budget and three sort chunks.  The constants of csrc/expr_ranksum.hip are
-read from the source."""
+non-finite key, two tiles of genes under the small budget and three sort chunks.  The constants of csrc/rank_sort.h and
+csrc/expr_rankcorr.hip are read from the source."""
 import functools
 
 import numpy as np

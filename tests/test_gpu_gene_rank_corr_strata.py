@@ -111,6 +111,20 @@ def test_one_key_and_sixteen_keys(eng, form, q):
     _same_bits(eng.gene_rank_corr_by(core_keys(q), strata_codes(), STRATA_LEVELS, SMALL_WORK_BYTES), got, ~got[5])
 
 
+@pytest.mark.parametrize('form', FORMS)
+def test_tiles_of_several_keys_and_a_shorter_last_one(eng, form):
+    """Five keys under 160 000 bytes: an entry of a key's segment costs 24 bytes, so 6666 entries fit and the keys of 3001
+    cells go two, two and one to a tile -- the second and third tiles begin at key 2 and key 4, where the key's index, its
+    first chunk, its first entry and its rows of the level pass' scan all matter.  The same budget cuts the dense genes into
+    tiles of two (float64) or three (float32).  The same bits as under the default budget, where all keys are one tile."""
+    assert 160000 // 24 // N_CORE == 2
+    eng.ensure_expression(core_input(form))
+    V, codes = core_keys(5), strata_codes()
+    got = eng.gene_rank_corr_by(V, codes, STRATA_LEVELS)
+    _equal('%s q=5' % form, got, strata_reference(form, 5))
+    _same_bits(eng.gene_rank_corr_by(V, codes, STRATA_LEVELS, 160000), got, ~got[5])
+
+
 @pytest.mark.parametrize('form', ['csc-f64', 'dense-f32'])
 def test_255_levels(eng, form):
     eng.ensure_expression(core_input(form))
