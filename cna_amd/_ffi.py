@@ -149,6 +149,8 @@ SIGNATURES = {
     'cna_gene_ranksum_by': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cna_gene_ranksum_pairs': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    'cna_gene_ranksum_within': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+                                + [C.c_void_p] * 6),
     'cna_gene_rank_corr': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 4 + [c_i64p, C.c_void_p]),
     'cna_gene_rank_corr_by': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 6),
     'cna_x_generation': (C.c_int, [c_ctx, C.POINTER(C.c_int64)]),

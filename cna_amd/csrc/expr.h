@@ -4,8 +4,8 @@
 // (nam_bins.hip: the NAM or X by bin, on this stream with this sort), cna_enrichment_extremes (enrich.hip: no matrix at all,
 // this stream and these buffers), cna_expr_cross_by (expr_cross_by.hip), cna_gram_by (gram_by.hip: X alone) and
 // cna_coef_raster (raster.hip: no matrix, this stream, the sort twice); cna_graph_components_* (components.hip) borrows the
-// stream and a slot of buffers and reads the resident graph; cna_gene_ranksum_by and cna_gene_ranksum_pairs
-// (expr_ranksum.hip: rank sums from a ranking of the cells of every gene) and cna_gene_rank_corr and cna_gene_rank_corr_by
+// stream and a slot of buffers and reads the resident graph; cna_gene_ranksum_by, cna_gene_ranksum_pairs and
+// cna_gene_ranksum_within (expr_ranksum.hip: rank sums from a ranking of the cells of every gene) and cna_gene_rank_corr and cna_gene_rank_corr_by
 // (expr_rankcorr.hip: Spearman's rho against per-cell columns from the same ranking), the two files sharing rank_sort.h: a
 // radix sort on the chunk tables, the walk over a sorted list and their buffers.  What two of them need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared

@@ -18,7 +18,15 @@
 //                         wave ballots, so that every tie run knows its cells per level and those below it; 2 U and the tie
 //                         term of every unordered pair of at most 64 levels in integer accumulators in LDS (stated at the
 //                         kernel)
+//
+// cna_gene_ranksum_within: every level against the rest INSIDE every block of a second column (samples, batches) and the
+// blocks folded with the caller's weights -- van Elteren's stratified rank-sum test (cna.tl.gene_markers_within) -- from
+// one sort with the cell as the payload and one more pass on the block of the entry's cell (rank_sort.h: `lvl8`).
+//   k_rs_within           behind that sort, one workgroup per gene: k_rs_rank's arithmetic on the sub-list of each block in
+//                         turn, then one thread per level folds the block into the level's integer sum and its two weighted
+//                         float64 sums, in block order and without FMA contraction
 #include "rank_sort.h"
+#include <cmath>
 
 namespace {
 
@@ -28,6 +36,7 @@ constexpr int RP_SLOTS = 2016;                 // their unordered pairs (the acc
 constexpr int RP_MAX_PAIRS = 2016;             // the pairs of one call
 constexpr int RP_BIG = 16;                     // a tie run of this many entries is added by the whole workgroup
 constexpr int RP_BIG_MOST = RS_UNIT / RP_BIG + 1;   // such runs that can end in one unit: one from before, the rest inside
+constexpr int RW_MAX_BLOCKS = 255;             // cna_gene_ranksum_within: the block is a digit of the sort, 255 = left out
 static_assert(RP_SLOTS == RP_MAX_LEVELS * (RP_MAX_LEVELS - 1) / 2, "one slot per unordered pair of levels");
 using CellList = CellListOf<RS_MAX_LEVELS>;
 
@@ -280,6 +289,132 @@ __global__ __launch_bounds__(RS_UNIT) void k_rs_pairs(const K* __restrict__ key,
   }
 }
 
+// ------------------------------------------------------------------ level against the rest inside every block
+// The operands of k_rs_within that do not depend on the gene, one upload (WithinTables::bytes): the weights of the tie
+// terms [block][level] and of the rank sums [block], the kept cells per (block, level) and per block.
+struct WithinTables {
+  const double *w_tie, *w_num;
+  const unsigned int *nsl, *ns;
+  static int64_t bytes(int n_blocks, int n_bins) { return (8 + 4) * ((int64_t)n_blocks * n_bins + n_blocks); }
+  static WithinTables at(void* p, int n_blocks, int n_bins) {
+    const int64_t cells = (int64_t)n_blocks * n_bins;
+    const double* d = static_cast<const double*>(p);
+    const unsigned int* u = reinterpret_cast<const unsigned int*>(d + cells + n_blocks);
+    return {d, d + cells, u, u + cells};
+  }
+};
+
+// acc + w x with the product and the sum rounded one after the other, as a numpy loop rounds them.  hipcc contracts
+// a * b + c into an FMA by default, and through __dmul_rn / __dadd_rn as well (plain operators in its headers: measured,
+// the sums came out one and two ulps off), so contraction is switched off for these two operations
+__device__ __forceinline__ double rw_mul_then_add(double acc, double w, double x) {
+#pragma clang fp contract(off)
+  const double p = w * x;
+  return acc + p;
+}
+
+// workgroup = gene g0 + blockIdx.x, behind the sort's pass on the block of the entry's cell: the gene's list is block-major
+// and sorted by value inside a block, block s in the positions [dbase[s], dbase[s + 1]) of its segment.  The blocks are
+// taken in order, each with k_rs_rank's arithmetic on its sub-list -- k stored kept entries among the n_s kept cells of the
+// block, z = n_s - k implicit zeros, the level of an entry read from codes[its cell] -- so that level b has twice its rank
+// sum inside the block and D = that - n_sb (n_s + 1).  Behind a block thread b (and b + RS_UNIT, ...) folds level b into
+// its accumulators: one thread per level and the blocks in order fix the order of the float adds, and the products and
+// sums are rounded one by one (rw_mul_then_add), which is what a numpy loop over the blocks does.  A block in which the gene is constant -- its zero group holds all n_s cells, or it stores
+// them all in one run -- counts for no level's `live`.
+// LDS: 40 bytes per level behind the kernel's own 4 KB (the scans), sized by the launch: 44 KB at 1024 levels, three
+// workgroups to a CU; 5.3 KB at 32 levels, where the 256 threads' registers and not the LDS bound the occupancy.
+template <typename K>
+__global__ __launch_bounds__(RS_UNIT) void k_rs_within(const K* __restrict__ key, const uint32_t* __restrict__ cell,
+                                                       const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,
+                                                       const unsigned int* __restrict__ dbase, const int32_t* __restrict__ codes,
+                                                       int64_t n, WithinTables tab, int n_bins, int n_blocks,
+                                                       long long* __restrict__ d2_out, double* __restrict__ num_out,
+                                                       double* __restrict__ tiew_out, int* __restrict__ live_out) {
+  constexpr K K0 = rs_key_zero<K>();
+  extern __shared__ unsigned long long within_lds[];
+  unsigned long long* sum = within_lds;                                       // [n_bins] each, the 8-byte arrays first
+  long long* d2 = reinterpret_cast<long long*>(sum + n_bins);
+  double* num = reinterpret_cast<double*>(d2 + n_bins);
+  double* tiew = num + n_bins;
+  unsigned int* stored = reinterpret_cast<unsigned int*>(tiew + n_bins);
+  int* live = reinterpret_cast<int*>(stored + n_bins);
+  __shared__ long long sh[RS_UNIT];
+  __shared__ double tsh[RS_UNIT];
+  __shared__ unsigned int below, zeros;
+  const int t = threadIdx.x;
+  const int64_t g = g0 + blockIdx.x;
+  key += seg[g] - base;
+  cell += seg[g] - base;
+  dbase += (int64_t)blockIdx.x * 256;
+  for (int b = t; b < n_bins; b += RS_UNIT) {
+    d2[b] = 0;
+    num[b] = 0.0;
+    tiew[b] = 0.0;
+    live[b] = 0;
+  }
+  for (int s = 0; s < n_blocks; ++s) {
+    const long long at = (long long)dbase[s], k = (long long)dbase[s + 1] - at;
+    const long long cells = (long long)tab.ns[s], z = cells - k;
+    const K* bkey = key + at;
+    const uint32_t* bcell = cell + at;
+    for (int b = t; b < n_bins; b += RS_UNIT) {
+      sum[b] = 0;
+      stored[b] = 0;
+    }
+    if (t == 0) below = zeros = 0;
+    __syncthreads();
+    RankWalkMine mine;
+    rs_walk_forward(bkey, k, sh, mine, [&](long long p, K kk, long long ps) {
+      const uint32_t cl = bcell[p];
+      const unsigned int l = (int64_t)cl < n ? (unsigned int)codes[cl] : ~0u;   // (a block's entries are kept cells')
+      if (l < (unsigned)n_bins) {
+        atomicAdd(&sum[l], (unsigned long long)(ps + (kk > K0 ? z : 0)));
+        atomicAdd(&stored[l], 1u);
+      }
+    });
+    rs_walk_backward(bkey, k, sh, [&](long long p, K kk, long long pe) {
+      const uint32_t cl = bcell[p];
+      const unsigned int l = (int64_t)cl < n ? (unsigned int)codes[cl] : ~0u;
+      if (l < (unsigned)n_bins) atomicAdd(&sum[l], (unsigned long long)(pe + (kk >= K0 ? z : 0)));
+    });
+    const RankWalkZero zero = rs_walk_fold(mine, z, tsh, &below, &zeros);
+    const bool constant = zero.t0 == cells || (z == 0 && k > 0 && bkey[0] == bkey[k - 1]);
+    const double wn = tab.w_num[s];
+    for (int b = t; b < n_bins; b += RS_UNIT) {
+      const long long st = (long long)stored[b], nl = (long long)tab.nsl[(int64_t)s * n_bins + b];
+      const long long rank2 = (long long)sum[b] + st + (nl - st) * (2 * zero.below + zero.t0 + 1);
+      const long long D = rank2 - nl * (cells + 1);
+      d2[b] += D;
+      num[b] = rw_mul_then_add(num[b], wn, (double)D);
+      tiew[b] = rw_mul_then_add(tiew[b], tab.w_tie[(int64_t)s * n_bins + b], zero.tie);
+      if (nl > 0 && nl < cells && !constant) ++live[b];
+    }
+    __syncthreads();                                  // sum, stored, below and zeros are read before the next block resets them
+  }
+  for (int b = t; b < n_bins; b += RS_UNIT) {         // (its own accumulators: no barrier is needed)
+    d2_out[(int64_t)b * G + g] = d2[b];
+    num_out[(int64_t)b * G + g] = num[b];
+    tiew_out[(int64_t)b * G + g] = tiew[b];
+    live_out[(int64_t)b * G + g] = live[b];
+  }
+}
+
+template <typename T>
+int within_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int n_blocks, int64_t work_bytes, int64_t m) {
+  using K = typename KeyOf<T>::K;
+  const int64_t G = s->G;
+  const WithinTables tab = WithinTables::at(w->wtab.p, n_blocks, n_bins);
+  return ranksum_sorted<T, uint32_t>(
+      c, s, w, work_bytes, m, "cna_gene_ranksum_within",
+      [&](const GeneTile& t, int64_t base, const K* key, const uint32_t* cell, const int64_t* seg) {
+        ProfScope ps(c, CNA_K_RANKSUM_RANK, s->st);
+        hipLaunchKernelGGL(k_rs_within<K>, dim3((unsigned)(t.g1 - t.g0)), dim3(RS_UNIT), (size_t)(40 * n_bins), s->st, key, cell,
+                           seg, base, t.g0, G, w->dbase.as<const unsigned int>(), w->sort.codes(), s->n, tab, n_bins, n_blocks,
+                           w->wd2.as<long long>(), w->wnum.as<double>(), w->wtiew.as<double>(), w->wlive.as<int>());
+      },
+      w->lvl8.as<const uint8_t>());
+}
+
 template <typename T>
 int ranksum_run(cna_ctx* c, ExprState* s, RankSumWork* w, int n_bins, int64_t work_bytes, int64_t m) {
   using K = typename KeyOf<T>::K;
@@ -355,6 +490,83 @@ extern "C" int cna_gene_ranksum_by(cna_ctx* c, const int32_t* codes, int n_bins,
         return s->is_f64 ? ranksum_run<double>(c, s, w, n_bins, work_bytes, m) : ranksum_run<float>(c, s, w, n_bins, work_bytes, m);
       },
       {rank2_out, &w->rank2, 8 * (int64_t)n_bins * s->G}, {tie_out, &w->tie, 8 * s->G}, n_out, nan_out);
+}
+
+// The codes are judged on the host here: the kept cells are an intersection of two columns and the table of their sizes has
+// up to 255 x 1024 cells, more than sort_count's counters in LDS hold; the caller's host has made the same pass over the
+// cells for its weights.
+extern "C" int cna_gene_ranksum_within(cna_ctx* c, const int32_t* codes, int n_bins, const int32_t* blocks, int n_blocks,
+                                       const double* w_num, const double* w_tie, int64_t work_bytes, int64_t* d2_out,
+                                       double* num_out, double* tiew_out, int32_t* live_out, int64_t* n_out, uint8_t* nan_out) {
+  CHECK_CTX(c);
+  const char* who = "cna_gene_ranksum_within";
+  ExprState* s = expr_state(c);
+  if (!s || s->format == 0) CNA_FAIL(CNA_ESTATE, "cna_gene_ranksum_within: no expression matrix is resident (cna_expr_upload_*)");
+  if (!codes || !blocks || !w_num || !w_tie || !d2_out || !num_out || !tiew_out || !live_out || !n_out || !nan_out)
+    CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_within: null pointer");
+  if (n_bins < 1 || n_bins > RS_MAX_LEVELS) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_within: 1 <= n_bins <= 1024");
+  if (n_blocks < 1 || n_blocks > RW_MAX_BLOCKS) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_within: 1 <= n_blocks <= 255");
+  if (work_bytes < 0) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_within: work_bytes is 0 (the default) or a number of bytes");
+  const int64_t n = s->n, G = s->G, cells = (int64_t)n_blocks * n_bins;
+  for (int64_t j = 0; j < cells + n_blocks; ++j)
+    if (!std::isfinite(j < cells ? w_tie[j] : w_num[j - cells])) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_within: a weight is not finite");
+  // the kept cells: a level and a block.  lev[i] = the level or -1, blk8[i] = the block or 255: the digit of the sort's last pass
+  std::vector<int32_t> lev((size_t)n);
+  std::vector<uint8_t> blk8((size_t)n);
+  std::vector<int64_t> nsl((size_t)cells, 0);
+  int64_t m = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t cd = codes[i], bl = blocks[i];
+    if (cd < -1 || cd >= n_bins) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_within: a level code lies outside [-1, n_bins)");
+    if (bl < -1 || bl >= n_blocks) CNA_FAIL(CNA_EINVAL, "cna_gene_ranksum_within: a block code lies outside [-1, n_blocks)");
+    const bool keep = cd >= 0 && bl >= 0;
+    lev[(size_t)i] = keep ? cd : -1;
+    blk8[(size_t)i] = keep ? (uint8_t)bl : (uint8_t)255;
+    if (keep) {
+      ++nsl[(size_t)bl * n_bins + cd];
+      ++m;
+    }
+  }
+  std::vector<unsigned char> tables((size_t)WithinTables::bytes(n_blocks, n_bins));
+  {
+    double* d = reinterpret_cast<double*>(tables.data());
+    unsigned int* u = reinterpret_cast<unsigned int*>(d + cells + n_blocks);
+    std::copy(w_tie, w_tie + cells, d);
+    std::copy(w_num, w_num + n_blocks, d + cells);
+    for (int b = 0; b < n_blocks; ++b) {
+      int64_t ns = 0;
+      for (int l = 0; l < n_bins; ++l) {
+        u[(int64_t)b * n_bins + l] = (unsigned int)nsl[(size_t)b * n_bins + l];
+        ns += nsl[(size_t)b * n_bins + l];
+      }
+      u[cells + b] = (unsigned int)ns;
+    }
+  }
+  RankSumWork* w = expr_work<RankSumWork>(s, EXPR_RANKSUM);
+  const int64_t out_count = (int64_t)n_bins * G;
+  CNA_TRY(result_bufs_need(c, s->st, {{&w->wd2, 8 * out_count}, {&w->wnum, 8 * out_count}, {&w->wtiew, 8 * out_count},
+                                      {&w->wlive, 4 * out_count}}));
+  CNA_TRY(buf_need(c, s->st, w->sort.code, 4 * n));
+  CNA_TRY(buf_need(c, s->st, w->lvl8, n));
+  CNA_TRY(buf_need(c, s->st, w->wtab, (int64_t)tables.size()));
+  HIP_TRY(hipMemcpyAsync(w->sort.code.p, lev.data(), (size_t)(4 * n), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemcpyAsync(w->lvl8.p, blk8.data(), (size_t)n, hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemcpyAsync(w->wtab.p, tables.data(), tables.size(), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));               // (the host vectors may go; the sort's own setup waits here anyway)
+  if (s->is_f64) CNA_TRY(within_run<double>(c, s, w, n_bins, n_blocks, work_bytes, m));
+  else CNA_TRY(within_run<float>(c, s, w, n_bins, n_blocks, work_bytes, m));
+  std::vector<unsigned int> nanf((size_t)G);
+  {
+    ProfScope ps(c, CNA_K_RANKSUM_FETCH, s->st);
+    CNA_TRY(fetch_results(s->st, who, {{d2_out, w->wd2.p, (size_t)(8 * out_count)},
+                                       {num_out, w->wnum.p, (size_t)(8 * out_count)},
+                                       {tiew_out, w->wtiew.p, (size_t)(8 * out_count)},
+                                       {live_out, w->wlive.p, (size_t)(4 * out_count)},
+                                       {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
+  }
+  for (int64_t g = 0; g < G; ++g) nan_out[g] = nanf[(size_t)g] ? 1 : 0;
+  for (int64_t j = 0; j < cells; ++j) n_out[j] = nsl[(size_t)j];
+  return 0;
 }
 
 extern "C" int cna_gene_ranksum_pairs(cna_ctx* c, const int32_t* codes, int n_bins, const int32_t* pairs, int n_pairs,

@@ -1,5 +1,5 @@
 // Private to expr_ranksum.hip (the rank sums) and expr_rankcorr.hip (Spearman): a ranking of the kept cells of every gene of
-// the resident matrix, which neither entry point owns, and the buffers the four entries share (RankSumWork).
+// the resident matrix, which neither entry point owns, and the buffers the five entries share (RankSumWork).
 //   k_rs_keys_sparse / k_rs_keys_dense
 //                         every entry of a gene's list, or of a 64 x 64 tile of the dense matrix, -> an order-preserving
 //                         unsigned key (-0.0 and a stored zero = the key of +0.0; float64 on all 64 bits) and its payload P,
@@ -30,7 +30,7 @@ constexpr int RS_UNIT = 256;                   // entries of a sorted list a wal
 constexpr int RS_TILE = 64;                    // the dense gather's square tile
 constexpr uint16_t RS_LEFT = 0xffff;           // "level" of an entry whose cell is left out (rs_left<uint16_t>())
 
-// The one slot EXPR_RANKSUM: the four entry points share keys, payloads, counters and the dense table.  One definition with
+// The one slot EXPR_RANKSUM: the five entry points share keys, payloads, counters and the dense table.  One definition with
 // external linkage: the translation unit that creates it and the one that casts to it (expr_work) mean the same type.
 struct RankSumWork : BufSet {
   CodeSort sort{*this};
@@ -41,6 +41,8 @@ struct RankSumWork : BufSet {
   // cna_gene_rank_corr: the columns, the kept cells' count, b[cell][W], the columns' tie terms (96 bits), the two limbs of S
   Buf vcol{*this}, vm{*this}, btab{*this}, tiek{*this}, slo{*this}, shi{*this};
   Buf lvl8{*this};                                                     // cna_gene_rank_corr_by: the kept cell's level as a byte
+  // cna_gene_ranksum_within (its blocks ride in lvl8): the weights and the sizes of its (block, level) table; the results
+  Buf wtab{*this}, wd2{*this}, wnum{*this}, wtiew{*this}, wlive{*this};
 };
 
 // What an entry carries through the sort beside its key.  All ones: the cell is left out.

@@ -1368,6 +1368,39 @@ class Engine(_order.CellOrder):
                                               ptr(tie), ptr(n), ptr(nan)), 'cna_gene_ranksum_pairs')
         return u2, tie, n, nan.astype(bool)
 
+    def gene_ranksum_within(self, codes, n_levels, blocks, n_blocks, w_num, w_tie, work_bytes=0):
+        """Every level of `codes` against the rest inside every block of `blocks` (both int32 per cell, -1 = cell left out;
+        at most 1024 levels and 255 blocks), ranked inside the block, the blocks folded with the caller's finite weights
+        `w_num` float64[n_blocks] and `w_tie` float64[n_blocks, n_levels] (cna_gene_ranksum_within).  With D = 2 x the
+        level's rank sum inside the block - n_sl (n_s + 1) and T the block's tie term, returns (d2 int64[n_levels, genes]:
+        the sum of D over the blocks, num float64[n_levels, genes]: w_num[s] * D folded in block order, tiew
+        float64[n_levels, genes]: w_tie[s, l] * T folded likewise, live int32[n_levels, genes]: blocks with 0 < n_sl < n_s
+        in which the gene is not constant, n int64[n_blocks, n_levels]: kept cells, nan bool[genes]: a kept cell holds NaN
+        and the gene's numbers mean nothing)."""
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        blocks = np.ascontiguousarray(blocks, dtype=np.int32)
+        n_levels, n_blocks = int(n_levels), int(n_blocks)
+        L, B = max(n_levels, 0), max(n_blocks, 0)
+        w_num = _f64(w_num)
+        w_tie = _f64(w_tie)
+        info = self.expression_shape()
+        if info['format'] != 'none' and (codes.shape != (info['n_cells'],) or blocks.shape != codes.shape):
+            raise ValueError('gene_ranksum_within: %d level codes and %d block codes for %d resident cells'
+                             % (codes.size, blocks.size, info['n_cells']))
+        if w_num.shape != (B,) or w_tie.shape != (B, L):
+            raise ValueError('gene_ranksum_within: weights %s and %s for %d blocks and %d levels'
+                             % (w_num.shape, w_tie.shape, n_blocks, n_levels))
+        G = info['n_genes']
+        d2 = np.empty((L, G), dtype=np.int64)
+        num, tiew = np.empty((L, G)), np.empty((L, G))
+        live = np.empty((L, G), dtype=np.int32)
+        n = np.empty((B, L), dtype=np.int64)
+        nan = np.empty(G, dtype=np.uint8)
+        check(self.lib.cna_gene_ranksum_within(self.h, ptr(codes), n_levels, ptr(blocks), n_blocks, ptr(w_num), ptr(w_tie),
+                                               int(work_bytes), ptr(d2), ptr(num), ptr(tiew), ptr(live), ptr(n), ptr(nan)),
+              'cna_gene_ranksum_within')
+        return d2, num, tiew, live, n, nan.astype(bool)
+
     def gene_rank_corr(self, V, work_bytes=0):
         """The integers of Spearman's rank correlation of every gene of the resident expression matrix with every row of V
         (q x cells float64, caller's cell order, 1 <= q <= 16; a cell where any row is non-finite is left out of the whole

@@ -8,7 +8,7 @@ from ._raster import coef_raster
 from ._populations import coef_populations
 from ._gene_strata import gene_corr_strata
 from ._gene_test_strata import gene_test_strata
-from ._gene_markers import gene_markers, gene_markers_pairs
+from ._gene_markers import gene_markers, gene_markers_pairs, gene_markers_within
 from ._gene_rank_corr import gene_rank_corr, gene_rank_corr_strata
 from ._nam_strata import nam_strata
 from ._gene_sets import gene_set_enrich, gene_set_test
@@ -22,6 +22,7 @@ __all__ = [
     'gene_corr_strata',
     'gene_markers',
     'gene_markers_pairs',
+    'gene_markers_within',
     'gene_rank_corr',
     'gene_rank_corr_strata',
     'gene_set_enrich',

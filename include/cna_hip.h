@@ -77,7 +77,8 @@ enum {
   CNA_K_COMPONENTS_UPLOAD, CNA_K_COMPONENTS_HOOK, CNA_K_COMPONENTS_FLATTEN, CNA_K_COMPONENTS_CHECK, CNA_K_COMPONENTS_TALLY,
   CNA_K_COMPONENTS_LABEL, CNA_K_COMPONENTS_FETCH,
   /* cna_gene_ranksum_by on the expression stream: the keys and levels of a tile of genes; the passes of the radix sort;
-   * the rank kernel; the copies of the results back (csrc/expr_ranksum.hip) */
+   * the rank kernel (in a cna_gene_ranksum_within call: its kernel over the blocks); the copies of the results back
+   * (csrc/expr_ranksum.hip) */
   CNA_K_RANKSUM_KEYS, CNA_K_RANKSUM_SORT, CNA_K_RANKSUM_RANK, CNA_K_RANKSUM_FETCH,
   /* cna_gene_ranksum_pairs: the kernel behind the sort (the keys, the sort and the copies back are counted under the ids
    * above) */
@@ -635,7 +636,7 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
  * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster, cna_graph_components_find,
- * cna_gene_ranksum_by, cna_gene_ranksum_pairs, cna_gene_rank_corr and cna_gene_rank_corr_by: cna_ctx_device_bytes returns to what it was before the upload. */
+ * cna_gene_ranksum_by, cna_gene_ranksum_pairs, cna_gene_ranksum_within, cna_gene_rank_corr and cna_gene_rank_corr_by: cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -781,6 +782,49 @@ int  cna_gene_ranksum_by(cna_ctx* ctx, const int32_t* codes, int n_bins, int64_t
  * not fit; the context stays usable. */
 int  cna_gene_ranksum_pairs(cna_ctx* ctx, const int32_t* codes, int n_bins, const int32_t* pairs, int n_pairs,
                             int64_t work_bytes, int64_t* u2_out, double* tie_out, int64_t* n_out, uint8_t* nan_out);
+/* Every level against the rest INSIDE every block of a second per-cell column (the sample or the batch), the blocks folded
+ * with the caller's weights: the integers and weighted sums of the stratified rank-sum test (van Elteren's test;
+ * cna.tl.gene_markers_within).  A population found by an association with a sample-level phenotype is over-represented in
+ * some samples by construction, so the pooled ranking of cna_gene_ranksum_by calls a gene a marker whose baseline differs
+ * between donors or batches; ranked inside each block such a gene shows nothing.
+ *   codes[i]   the level of cell i in [0, n_bins), or -1;   1 <= n_bins <= 1024
+ *   blocks[i]  the block of cell i in [0, n_blocks), or -1;  1 <= n_blocks <= 255 (the block is one digit of the sort and
+ *              255 stands for a left-out entry, as the level does in cna_gene_rank_corr_by)
+ *   w_num[s], w_tie[s * n_bins + l]   finite weights of block s: of its centred rank sums and, per level, of its tie term
+ *   work_bytes  as in cna_gene_ranksum_by, for {key, cell} entries: 2 x (4 or 8, + 4) bytes each
+ * The KEPT cells are those with a level code >= 0 AND a block code >= 0.  For block s, level l and gene g: n_s the kept
+ * cells of the block, n_sl those of level l, R_gsl the sum over the level's cells of their midranks inside the block, T_gs
+ * the sum of t^3 - t over the gene's tie groups inside the block, under the value rules of cna_gene_ranksum_by (-0.0 =
+ * +0.0 = a stored zero = the implicit zeros, +-inf ordinary values, float64 ranked on all 64 bits).
+ * D_gsl = 2 R_gsl - n_sl (n_s + 1) is an integer, twice the centred rank sum: D / 2 = U_gsl - n_sl (n_s - n_sl) / 2.
+ *   n_out[s * n_bins + l] = n_sl
+ *   d2_out[l * n_genes + g] = sum over s of D_gsl, exact; |sum| <= m^2 for m kept cells
+ *   num_out[l * n_genes + g]: acc = +0.0; for s = 0 .. n_blocks - 1 in that order, empty blocks included,
+ *             acc = acc + w_num[s] * (double)D_gsl, the product and the sum rounded separately (no FMA contraction): the
+ *             bits of that loop in numpy
+ *   tiew_out[l * n_genes + g]: the same fold of w_tie[s * n_bins + l] * T_gs, T_gs a double formed like
+ *             cna_gene_ranksum_by's tie_out (exact below 2^53)
+ *   live_out[l * n_genes + g] = the blocks with 0 < n_sl < n_s in which gene g is not constant, decided from the tie runs
+ *             (the zero group holds all n_s cells, or all n_s are stored in one run), not from a floating comparison
+ *   nan_out[g] = 1 when a kept cell of ANY block holds NaN in gene g (the gene's other outputs are then unspecified)
+ * Behind the value passes of cna_gene_ranksum_by's sort, with the cell as the entry's payload, one more stable pass takes
+ * the block of the entry's cell as its digit, which leaves every gene's list block-major and sorted inside a block, the scan
+ * of that pass saying where each (gene, block) begins: one sort instead of one per block.  One workgroup per gene then
+ * takes the blocks in order: cna_gene_ranksum_by's walk on the block's sub-list with n_s cells, its stored entries and
+ * n_s - stored implicit zeros, the level read from codes[cell], per-level integer sums in LDS; behind a block one thread
+ * per level folds it into the level's accumulators, which fixes the order of the float adds.
+ * The same bits on every run, under every work_bytes and for a CSR and a CSC upload of one matrix.  Runs on the expression
+ * stream with the work buffers of cna_gene_ranksum_by (grow-only, freed by cna_expr_drop), changes no other state, works
+ * on a context that never saw a graph and may be called between cna_null_local_launch and cna_null_local_fetch.  Its
+ * kernel behind the sort is timed under CNA_K_RANKSUM_RANK, the keys, the sort and the copies back under _KEYS, _SORT
+ * and _FETCH.
+ * CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL, with nothing written: a null pointer, n_bins, n_blocks or
+ * work_bytes out of range, a weight that is not finite, a level code outside [-1, n_bins) or a block code outside
+ * [-1, n_blocks) (checked on the host, with the table of n_sl).  CNA_ENOMEM: the four n_bins x n_genes result buffers do
+ * not fit; the context stays usable. */
+int  cna_gene_ranksum_within(cna_ctx* ctx, const int32_t* codes, int n_bins, const int32_t* blocks, int n_blocks,
+                             const double* w_num, const double* w_tie, int64_t work_bytes, int64_t* d2_out, double* num_out,
+                             double* tiew_out, int32_t* live_out, int64_t* n_out, uint8_t* nan_out);
 
 /* Spearman's rank correlation of every gene with 1 <= q <= 16 per-cell columns (cna.tl.gene_rank_corr), from the same sort
  * with the cell as the entry's payload: invariant to log1p, scaling and every other monotone normalisation of X or of a
