@@ -5,15 +5,18 @@
 // this stream and these buffers), cna_expr_cross_by (expr_cross_by.hip), cna_gram_by (gram_by.hip: X alone) and
 // cna_coef_raster (raster.hip: no matrix, this stream, the sort twice); cna_graph_components_* (components.hip) borrows the
 // stream and a slot of buffers and reads the resident graph; cna_gene_ranksum_by, cna_gene_ranksum_pairs and
-// cna_gene_ranksum_within (expr_ranksum.hip: rank sums from a ranking of the cells of every gene) and cna_gene_rank_corr and cna_gene_rank_corr_by
-// (expr_rankcorr.hip: Spearman's rho against per-cell columns from the same ranking), the two files sharing rank_sort.h: a
+// cna_gene_ranksum_within (expr_ranksum.hip: rank sums from a ranking of the cells of every gene), cna_gene_rank_corr and
+// cna_gene_rank_corr_by (expr_rankcorr.hip: Spearman's rho against per-cell columns from the same ranking) and
+// cna_gene_rank_corr_x, cna_gene_rank_corr_wide and cna_x_columns (expr_rankperm.hip: rho against up to 4096 columns, formed
+// from X or given, from one sort), the three files sharing rank_sort.h: a
 // radix sort on the chunk tables, the walk over a sorted list and their buffers.  What two of them need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared
 //   ExprState       the resident matrix, the stream, and one slot of work buffers per entry point
 //   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins and cna_gene_corr_by, value
 //                   segments of cna_coef_strata): one count kernel, one fill kernel, one host half; CellListOf
 //   gene_tiles      the walk over tiles of whole genes of the gene-major kernels
-//   xrow_check      the verdict on a map cells -> rows of X (cna_expr_cross and the two entries by level)
+//   xrow_check      the verdict on a map cells -> rows of X (cna_expr_cross, the two entries by level, the two of
+//                   expr_rankperm.hip that read X)
 //   with_bool / with_width, fetch_results, result_bufs_need, finite_d, wave_min / wave_max
 // Templates are instantiated where they are used; nothing here needs relocatable device code.
 #pragma once

@@ -1,7 +1,8 @@
 // cna_gene_rank_corr: Spearman's rank correlation of every gene of the resident expression matrix with up to 16 per-cell
 // columns (cna.tl.gene_rank_corr), as exact integers.  The genes are sorted with the cell as an entry's payload (uint32_t),
 // and the columns are ranked by the same passes (rank_sort.h): rs_passes knows a chunk table and nothing of the matrix.
-//   k_rc_mask             the kept cells (every column finite) as the codes ranksum_sorted expects, and their number m
+//   k_rc_mask             (rank_corr.h, shared with expr_rankperm.hip) the kept cells (every column finite) as the codes
+//                         ranksum_sorted expects, and their number m
 //   k_rc_vkeys            the columns as q segments of n entries {float64 key, cell} in a table of the dense form's shape
 //   k_rc_keyrank          behind their sort, one thread per kept entry: its tie run [s, e), by binary search where a neighbour
 //                         ties -> b = s + e - m (twice the midrank less m + 1) into the cell-major table btab[cell][W]; the
@@ -18,49 +19,16 @@
 // level) begins.  k_rc_keyrank<true> keeps its searches inside the level's range and k_rc_corr runs once per (gene, level)
 // on the sub-segment (GeneLevel) with the level's m_l, k_l and z_l: level l is cna_gene_rank_corr on columns set to NaN
 // outside l, integer for integer.
-#include "rank_sort.h"
+#include "rank_corr.h"
 
 namespace {
 
-constexpr int RC_MAX_KEYS = 16;                // per-cell columns of one call
 constexpr int RC_MAX_LEVELS = 255;             // cna_gene_rank_corr_by: the level is a digit of the sort, 255 = left out
 
 // With r the midrank over the m kept cells, a_i = 2 r_gene(i) - (m + 1) and b_i = 2 r_column(i) - (m + 1) are integers
 // that sum to 0 over the kept cells, and a tie run [s, e) of a sorted list gives each of its entries s + e - m.
 //   S[k, g] = sum over the kept cells of a_i b_i[k]      rho = 3 S / sqrt((m^3 - m - T_g) (m^3 - m - T_k))   (the host's line)
 // |S| <= (m^3 - m) / 3 passes 2^63 from 3 024 617 cells on, so S is summed and returned in 128 bits.
-
-// codes[i] = 0 where every column is finite, else -1; *m += their number.  BY (cna_gene_rank_corr_by): codes holds the
-// caller's levels, all in [-1, n_bins) with n_bins <= 255; a cell keeps its level where every column is finite, else -1;
-// lvl8[i] = that level as a byte, 255 for -1 (the digit of the sort's last pass); m[l] += the kept cells of level l
-template <bool BY>
-__global__ __launch_bounds__(256) void k_rc_mask(const double* __restrict__ V, int q, int64_t n, int32_t* __restrict__ codes,
-                                                 uint8_t* __restrict__ lvl8, unsigned long long* __restrict__ m) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  bool keep = i < n;
-  if constexpr (BY) {
-    __shared__ unsigned int h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    if (i < n) {
-      const int32_t cd = codes[i];
-      keep = cd >= 0;
-      for (int k = 0; k < q; ++k) keep = keep && finite_d(V[(int64_t)k * n + i]);
-      codes[i] = keep ? cd : -1;
-      lvl8[i] = keep ? (uint8_t)cd : (uint8_t)255;
-      if (keep) atomicAdd(&h[cd & 255], 1u);
-    }
-    __syncthreads();
-    if (h[threadIdx.x]) atomicAdd(&m[threadIdx.x], (unsigned long long)h[threadIdx.x]);
-  } else {
-    if (i < n) {
-      for (int k = 0; k < q; ++k) keep = keep && finite_d(V[(int64_t)k * n + i]);
-      codes[i] = keep ? 0 : -1;
-    }
-    const unsigned long long bal = __ballot(keep);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(m, (unsigned long long)__popcll(bal));
-  }
-}
 
 // column k0 + blockIdx.y as a segment of n entries {key of the float64 value, cell}; a left-out cell sorts behind the kept
 __global__ __launch_bounds__(256) void k_rc_vkeys(const double* __restrict__ V, int64_t n, int k0,
@@ -151,12 +119,6 @@ __global__ __launch_bounds__(256) void k_rc_keyrank(const uint64_t* __restrict__
   __syncthreads();
   if (threadIdx.x == 0) rp_add128(&tie_lo[first_level * RC_MAX_KEYS + col], &tie_hi[first_level * RC_MAX_KEYS + col], {tl, (unsigned long long)th});
 }
-
-// one cell's row of btab: W columns (the least of 1, 2, 4, 8, 16 that holds q), one aligned load
-template <int W>
-struct alignas(4 * W) BRow {
-  int32_t v[W];
-};
 
 // workgroup = gene g0 + blockIdx.x over its kept[g] sorted entries {key, cell}.  a_i = s + e - m splits into a walk forward
 // (s - m, in [-m, 0)) and one backward (e, in [1, m]), with their shifts by the z implicit zeros; each walk gathers the
@@ -274,11 +236,14 @@ __global__ __launch_bounds__(RS_UNIT) void k_rc_corr(const K* __restrict__ key, 
   }
 }
 
+}  // namespace
+
 // The columns' ranks: tiles of whole columns within the budget, each a segment of n entries in a table of the dense form's
 // shape; sorted by the same passes, then k_rc_keyrank writes btab and the tie terms.  With `lvl8` (cna_gene_rank_corr_by)
-// the passes end on the level and the ranks are those inside it.
-int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, int64_t work_bytes, int64_t m, int n_bins,
-                  const uint8_t* lvl8, const char* who) {
+// the passes end on the level and the ranks are those inside it.  Declared in rank_corr.h: expr_rankperm.hip calls it once
+// per group of 16 columns, each with a table and tie slots of its own.
+int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, int64_t work_bytes, int64_t m,
+                  const uint8_t* lvl8, int32_t* btab, unsigned long long* tie_lo, unsigned int* tie_hi, const char* who) {
   const int64_t n = s->n;
   std::vector<int64_t> seg_h, gchunk_h;
   SortTable tb;
@@ -289,8 +254,6 @@ int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, i
   CNA_TRY((rs_sort_bufs<uint64_t, uint32_t>(c, s, w, ts.entries, ts.chunks, ts.segs)));
   uint64_t *ka = w->keyA.as<uint64_t>(), *kb = w->keyB.as<uint64_t>();
   uint32_t *pa = w->lvlA.as<uint32_t>(), *pb = w->lvlB.as<uint32_t>();
-  unsigned long long* tie_lo = w->tiek.as<unsigned long long>();
-  unsigned int* tie_hi = w->tiek.as<unsigned int>() + 2 * RC_MAX_KEYS * n_bins;
   for (const GeneTile& t : ts.tiles) {                // its "genes" are the columns [g0, g1)
     const int k0 = (int)t.g0;
     const unsigned cols = (unsigned)(t.g1 - t.g0);
@@ -308,15 +271,17 @@ int rankcorr_keys(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int stride, i
     const dim3 grid((unsigned)((m + 255) / 256), cols);
     if (m > 0 && lvl8)
       hipLaunchKernelGGL(k_rc_keyrank<true>, grid, dim3(256), 0, s->st, (const uint64_t*)kb, (const uint32_t*)pb, n, k0,
-                         (long long)m, stride, w->btab.as<int32_t>(), tie_lo, tie_hi, lvl8, w->dbase.as<const unsigned int>());
+                         (long long)m, stride, btab, tie_lo, tie_hi, lvl8, w->dbase.as<const unsigned int>());
     else if (m > 0)
       hipLaunchKernelGGL(k_rc_keyrank<false>, grid, dim3(256), 0, s->st, (const uint64_t*)ka, (const uint32_t*)pa, n, k0,
-                         (long long)m, stride, w->btab.as<int32_t>(), tie_lo, tie_hi, (const uint8_t*)nullptr,
+                         (long long)m, stride, btab, tie_lo, tie_hi, (const uint8_t*)nullptr,
                          (const unsigned int*)nullptr);
   }
   HIP_TRY(hipGetLastError());
   return 0;
 }
+
+namespace {
 
 template <typename T>
 int rankcorr_run(cna_ctx* c, ExprState* s, RankSumWork* w, int q, int64_t work_bytes, int64_t m, int n_bins, const uint8_t* lvl8,
@@ -386,7 +351,8 @@ int rankcorr_entry(cna_ctx* c, ExprState* s, const char* who, const double* V, i
   }
   int64_t m = 0;
   for (int b = 0; b < n_bins; ++b) m += (int64_t)mlev[(size_t)b];
-  CNA_TRY(rankcorr_keys(c, s, w, q, stride, work_bytes, m, n_bins, lvl8, who));
+  CNA_TRY(rankcorr_keys(c, s, w, q, stride, work_bytes, m, lvl8, w->btab.as<int32_t>(), w->tiek.as<unsigned long long>(),
+                        w->tiek.as<unsigned int>() + 2 * RC_MAX_KEYS * n_bins, who));
   if (s->is_f64) CNA_TRY(rankcorr_run<double>(c, s, w, q, work_bytes, m, n_bins, lvl8, who));
   else CNA_TRY(rankcorr_run<float>(c, s, w, q, work_bytes, m, n_bins, lvl8, who));
   std::vector<unsigned int> nanf((size_t)G);

@@ -1,5 +1,5 @@
-// Private to expr_ranksum.hip (the rank sums) and expr_rankcorr.hip (Spearman): a ranking of the kept cells of every gene of
-// the resident matrix, which neither entry point owns, and the buffers the five entries share (RankSumWork).
+// Private to expr_ranksum.hip (the rank sums), expr_rankcorr.hip and expr_rankperm.hip (Spearman): a ranking of the kept
+// cells of every gene of the resident matrix, which no entry point owns, and the buffers the entries share (RankSumWork).
 //   k_rs_keys_sparse / k_rs_keys_dense
 //                         every entry of a gene's list, or of a 64 x 64 tile of the dense matrix, -> an order-preserving
 //                         unsigned key (-0.0 and a stored zero = the key of +0.0; float64 on all 64 bits) and its payload P,
@@ -41,6 +41,9 @@ struct RankSumWork : BufSet {
   // cna_gene_rank_corr: the columns, the kept cells' count, b[cell][W], the columns' tie terms (96 bits), the two limbs of S
   Buf vcol{*this}, vm{*this}, btab{*this}, tiek{*this}, slo{*this}, shi{*this};
   Buf lvl8{*this};                                                     // cna_gene_rank_corr_by: the kept cell's level as a byte
+  // cna_gene_rank_corr_x / _wide (expr_rankperm.hip): the tables b[group][cell][16] and the tie terms of every group of 16
+  // columns; a = s + e - m of every entry of a tile of genes and a_0 of every gene; xrow with its verdict, Z, the columns
+  Buf btabs{*this}, tieks{*this}, aent{*this}, azero{*this}, xrow{*this}, xseen{*this}, xflag{*this}, zrows{*this}, xcols{*this};
   // cna_gene_ranksum_within (its blocks ride in lvl8): the weights and the sizes of its (block, level) table; the results
   Buf wtab{*this}, wd2{*this}, wnum{*this}, wtiew{*this}, wlive{*this};
 };

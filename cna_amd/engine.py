@@ -1447,7 +1447,63 @@ class Engine(_order.CellOrder):
                                              ptr(tie_gene), ptr(tie_key), ptr(m), ptr(nan)), 'cna_gene_rank_corr_by')
         return s_lo, s_hi, tie_gene, tie_key, m, nan.astype(bool)
 
-    BW_KINDS = ('scott', 'silverman', 'constant')
+    def _x_columns_args(self, xrow, Z, who):
+        """(xrow int64, Z float64 C-contiguous, q, expression_shape()) of the entries that form per-cell columns from the working matrix X: one
+        rank with a replicated view, one xrow per resident cell, one row of Z per column with one entry per sample of X."""
+        if self.nranks != 1 or self.view_local:
+            raise NotImplementedError('%s needs every row of X on this rank (one rank, replicated view)' % who)
+        xrow = np.ascontiguousarray(xrow, dtype=np.int64)
+        Z = _f64(Z)
+        info = self.expression_shape()
+        if info['format'] != 'none':
+            cols = self.matrix_shape(MAT_X)[1]
+            if xrow.shape != (info['n_cells'],) or Z.ndim != 2 or Z.shape[1] != cols:
+                raise ValueError('%s: xrow %s and Z %s for %d resident cells and %d samples of X'
+                                 % (who, xrow.shape, Z.shape, info['n_cells'], cols))
+        return xrow, Z, (int(Z.shape[0]) if Z.ndim == 2 else 0), info
+
+    def x_columns(self, xrow, Z):
+        """float64[q, cells]: out[j, i] = sum over the samples s, ascending, of X[xrow[i], s] * Z[j, s] -- each product
+        rounded, then added -- for the cells with a row in the working matrix X (`x_row_of_cells`), NaN where xrow[i] is -1
+        (cna_x_columns).  Z: q x samples, 1 <= q <= 4096.  One rank, replicated view.  No memo."""
+        xrow, Z, q, info = self._x_columns_args(xrow, Z, 'x_columns')
+        out = np.empty((max(q, 0), len(xrow)))
+        check(self.lib.cna_x_columns(self.h, ptr(xrow), len(xrow), ptr(Z), q, ptr(out)), 'cna_x_columns')
+        return out
+
+    def _rank_corr_outputs(self, q, G):
+        return (np.empty((max(q, 0), G), dtype=np.uint64), np.empty((max(q, 0), G), dtype=np.int64), np.empty(G),
+                np.empty(max(q, 0)), C.c_int64(0), np.empty(G, dtype=np.uint8))
+
+    def gene_rank_corr_x(self, xrow, Z, work_bytes=0):
+        """`gene_rank_corr`'s integers for the q columns `x_columns(xrow, Z)` forms, 1 <= q <= 4096, from one sort of the
+        resident matrix whatever q is (cna_gene_rank_corr_x): the columns are formed and ranked on the device in groups
+        of 16.  The kept cells are those with xrow[i] >= 0; a formed value that is not finite is refused.  Returns
+        `gene_rank_corr`'s tuple.  One rank, replicated view.  No memo: the columns differ with every phenotype."""
+        xrow, Z, q, info = self._x_columns_args(xrow, Z, 'gene_rank_corr_x')
+        s_lo, s_hi, tie_gene, tie_key, m, nan = self._rank_corr_outputs(q, info['n_genes'])
+        check(self.lib.cna_gene_rank_corr_x(self.h, ptr(xrow), len(xrow), ptr(Z), q, int(work_bytes), ptr(s_lo), ptr(s_hi),
+                                            ptr(tie_gene), ptr(tie_key), C.byref(m), ptr(nan)), 'cna_gene_rank_corr_x')
+        return s_lo, s_hi, tie_gene, tie_key, int(m.value), nan.astype(bool)
+
+    def gene_rank_corr_wide(self, V, work_bytes=0):
+        """`gene_rank_corr` for 1 <= q <= 4096 rows of V (q x cells float64) from one sort of the resident matrix
+        (cna_gene_rank_corr_wide): the kept cells are those where every one of the q rows is finite, one set per call.
+        Returns `gene_rank_corr`'s tuple; every group of 16 rows holds what `gene_rank_corr` returns for those rows under
+        that kept set.  One rank, replicated view."""
+        if self.nranks != 1 or self.view_local:
+            raise NotImplementedError('gene_rank_corr_wide needs every cell on this rank (one rank, replicated view)')
+        V = _f64(V)
+        info = self.expression_shape()
+        if info['format'] != 'none' and (V.ndim != 2 or V.shape[1] != info['n_cells']):
+            raise ValueError('gene_rank_corr_wide: keys %s for %d resident cells' % (V.shape, info['n_cells']))
+        q = int(V.shape[0]) if V.ndim == 2 else 0
+        s_lo, s_hi, tie_gene, tie_key, m, nan = self._rank_corr_outputs(q, info['n_genes'])
+        check(self.lib.cna_gene_rank_corr_wide(self.h, ptr(V), q, int(work_bytes), ptr(s_lo), ptr(s_hi), ptr(tie_gene),
+                                               ptr(tie_key), C.byref(m), ptr(nan)), 'cna_gene_rank_corr_wide')
+        return s_lo, s_hi, tie_gene, tie_key, int(m.value), nan.astype(bool)
+
+    BW_KINDS =('scott', 'silverman', 'constant')
 
     def coef_strata(self, v, fdr, codes, n_bins, fdr_thresh, points, bw_kind='scott', bw_value=0.0):
         """Per-bin statistics and kernel densities of a per-cell column (cna_coef_strata): `v` float64 per cell in the

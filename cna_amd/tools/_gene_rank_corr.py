@@ -77,8 +77,8 @@ def gene_rank_corr(data, keys='coef', layer=None, key_added=None, engine=None):
     Returns a float64 DataFrame (index ``data.var_names`` when there are any), one column per key; ``key_added`` (a
     prefix) also writes ``data.var[key_added + key]``.
 
-    Not here: p-values (cells are not independent, so the t approximation would be anti-conservative: ``gene_test`` is
-    the answer to that, and a rank version of it is not built), Kendall's tau, gene-gene
+    Not here: p-values (cells are not independent, so the t approximation would be anti-conservative: the answer to that
+    is a permutation null, ``gene_rank_test`` for this rho as ``gene_test`` is for r), Kendall's tau, gene-gene
     rank correlations, a kept set per key, more than 16 keys per call, sharded data."""
     engine = engine or get_engine()
     refuse_sharded(data, engine, 'gene_rank_corr', 'the ranking runs over all cells of a gene: the rows of other ranks are elsewhere')

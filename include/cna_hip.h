@@ -85,7 +85,9 @@ enum {
   CNA_K_RANKSUM_PAIRS,
   /* cna_gene_rank_corr: the ranks of the columns (their upload, the kept cells, the kernel behind their sort) and the
    * correlation kernel behind the genes' sort; the keys, both sorts and the copies back are counted under
-   * CNA_K_RANKSUM_KEYS, _SORT and _FETCH */
+   * CNA_K_RANKSUM_KEYS, _SORT and _FETCH.  cna_gene_rank_corr_x / _wide (and cna_x_columns): the kernel that forms the
+   * columns from X, or their upload, under CNA_K_RANKCORR_KEYS beside the ranks; the kernel that stores a per entry under
+   * CNA_K_RANKSUM_RANK; the dot kernel under CNA_K_RANKCORR_CORR */
   CNA_K_RANKCORR_KEYS, CNA_K_RANKCORR_CORR,
   CNA_K_COUNT
 };
@@ -885,6 +887,49 @@ int  cna_gene_rank_corr(cna_ctx* ctx, const double* V, int q, int64_t work_bytes
 int  cna_gene_rank_corr_by(cna_ctx* ctx, const double* V, int q, const int32_t* codes, int n_bins, int64_t work_bytes,
                            uint64_t* s_lo_out, int64_t* s_hi_out, double* tie_gene_out, double* tie_key_out, int64_t* m_out,
                            uint8_t* nan_out);
+
+/* ---- Spearman's rho under the permuted phenotypes (csrc/expr_rankperm.hip) -------------------- */
+/* cna.tl.gene_rank_test: cna_gene_rank_corr against the null coefficients of the association's permuted phenotypes.  The
+ * null coefficient of a conditioned, standardised null phenotype z_p is c_p = X z_p per cell (reference
+ * _association.py:94-99, with X the residualised NAM; the observed one is _association.py:77).  Ranks are not linear in
+ * z_p, so -- unlike cna_expr_cross, which serves the Pearson null from W = E^T X alone -- every c_p is formed, ranked and
+ * correlated with every gene's ranks.  The three entries run on the expression stream with the work buffers of
+ * cna_gene_ranksum_by (grow-only, freed by cna_expr_drop); X is read and left as it is (the expression stream waits for
+ * what the main stream has queued that produces X, as in cna_expr_cross; cna_x_generation does not move).  Every argument
+ * is judged before anything is written, and the caller's buffers are written only after everything has succeeded.
+ *
+ * The columns alone:
+ *   Z[j * n_cols + s]   row j of q, 1 <= q <= 4096, one row per column to form; n_cols = the samples of X, <= 1024
+ *   xrow[i]             the row of X of cell i of the expression matrix (CALLER's cell order, n_cells entries), -1 for a
+ *                       cell that has none: cna_expr_cross's map, judged by its check with its verdicts and messages
+ *   out[j * n_cells + i] = sum over s of X[xrow[i]][s] * Z[j][s] for xrow[i] >= 0, NaN where xrow[i] == -1
+ * float64 throughout, the samples in ascending order, each product rounded on its own and then added to the running sum
+ * (no fused multiply-add): the bits of `acc = zeros; for s: acc = acc + X[rows, s] * Z[j, s]` in numpy.
+ * CNA_ESTATE: no expression matrix is resident, X not available, a communicator is active.  CNA_EINVAL: a null pointer,
+ * another length than the matrix' cells, q or the samples of X out of range, a bad xrow.  CNA_ENOMEM: q x n_cells
+ * float64 do not fit on the device. */
+int  cna_x_columns(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, const double* Z, int q, double* out);
+/* The integers of cna_gene_rank_corr for the q columns cna_x_columns forms, 1 <= q <= 4096, from ONE sort of the matrix.
+ * The kept cells are those with xrow[i] >= 0 -- the set does not depend on the column -- so a formed value that is not
+ * finite (an inf or a NaN in X or Z) is refused with CNA_EINVAL.  Outputs as cna_gene_rank_corr's: s_lo_out, s_hi_out
+ * [q, n_genes], tie_gene_out [n_genes], tie_key_out [q], *m_out, nan_out [n_genes].
+ * The columns go in groups of 16: formed into a 16 x n_cells buffer, ranked by cna_gene_rank_corr's passes, b = s + e - m
+ * written to the group's own cell-major table [cell][16] of int32.  All tables stay resident: 64 x ceil(q / 16) x n_cells
+ * bytes.  Then every tile of genes is sorted once (work_bytes as in cna_gene_rank_corr); behind it one workgroup per gene
+ * walks its list forward and backward once and stores a = s + e - m per entry, and one workgroup per (gene, group)
+ * streams {a, cell}, gathers the cell's 64-byte row and adds a x b per column in cna_gene_rank_corr's integer
+ * accumulators.  For every group of 16 columns the results equal cna_gene_rank_corr's on those columns under the same kept
+ * set, integer for integer, under every work_bytes and on every run.
+ * CNA_ESTATE, CNA_EINVAL as cna_x_columns, and a negative work_bytes.  CNA_ENOMEM: the tables or the results do not fit. */
+int  cna_gene_rank_corr_x(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, const double* Z, int q, int64_t work_bytes,
+                          uint64_t* s_lo_out, int64_t* s_hi_out, double* tie_gene_out, double* tie_key_out, int64_t* m_out,
+                          uint8_t* nan_out);
+/* The same core with the columns given by the host: V[k * n_cells + i], 1 <= q <= 4096.  The kept cells are those where
+ * EVERY one of the q columns is finite: one set per call, as in cna_gene_rank_corr, found in a first pass over V before
+ * any column is ranked.  Needs no X and no graph.  CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL: a null
+ * pointer, q outside [1, 4096], a negative work_bytes.  CNA_ENOMEM: the tables or the results do not fit. */
+int  cna_gene_rank_corr_wide(cna_ctx* ctx, const double* V, int q, int64_t work_bytes, uint64_t* s_lo_out, int64_t* s_hi_out,
+                             double* tie_gene_out, double* tie_key_out, int64_t* m_out, uint8_t* nan_out);
 
 /* ---- the expression matrix against the working matrix (csrc/expr_cross.hip) ------------------- */
 /* What cna.tl.gene_test needs from the cells: with c_p = X^T z_p / N the coefficient of a permuted, conditioned phenotype
