@@ -317,9 +317,10 @@ def test_long_genes_span_three_sort_chunks_the_last_one_ragged(form):
         assert chunks[0] == 0 and chunks[5] == 1
 
 
-def ranksum_tiles(form, work_bytes):
-    """ranksum_run: tiles of whole genes whose entries fit work_bytes / (2 * (key bytes + 2)), one gene at least"""
-    X = core_input(form)
+def ranksum_tiles(form, work_bytes, X=None):
+    """ranksum_run: tiles of whole genes whose entries fit work_bytes / (2 * (key bytes + 2)), one gene at least; of the core
+    input in that form, or of the matrix X of that form"""
+    X = core_input(form) if X is None else X
     key = 4 if form.endswith('f32') else 8
     limit = max(1, (work_bytes or ranksum_constant('RS_WORK_BYTES')) // (2 * (key + 2)))
     length = np.diff(sp.csc_matrix(X).indptr) if sp.issparse(X) else np.full(X.shape[1], X.shape[0])

@@ -252,10 +252,11 @@ def test_long_genes_and_keys_span_three_sort_chunks_the_last_one_ragged(form):
     assert -(-N_CORE // dense) >= 3 and N_CORE % dense != 0
 
 
-def rank_corr_tiles(form, work_bytes):
+def rank_corr_tiles(form, work_bytes, X=None):
     """ranksum_sorted with the cell as the payload: tiles of whole genes whose entries fit work_bytes / (2 * (key bytes + 4)),
-    one gene at least; rankcorr_keys: the columns that fit work_bytes / (2 * (8 + 4)) entries, one at least"""
-    X = core_input(form)
+    one gene at least; rankcorr_keys: the columns that fit work_bytes / (2 * (8 + 4)) entries, one at least; of the core input
+    in that form, or of the matrix X of that form"""
+    X = core_input(form) if X is None else X
     key = 4 if form.endswith('f32') else 8
     budget = work_bytes or ranksum_constant('RS_WORK_BYTES')
     limit = max(1, budget // (2 * (key + 4)))
