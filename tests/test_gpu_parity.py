@@ -573,7 +573,9 @@ def test_rccl_path_with_one_rank(orc, monkeypatch, selftest):
 
 @pytest.mark.parametrize('N,P,r,ks', [(50, 1001, 0, [1, 2, 3, 4]), (24, 37, 2, [2, 5]), (200, 300, 5, [4, 8, 12, 16]),
                                        (12, 5, 0, [1]), (130, 64, 1, [3, 26]), (200, 10001, 5, [4, 8, 12, 16]),
-                                       (600, 333, 2, [12, 24, 36, 48, 100]), (1024, 50, 0, [20, 40])])
+                                       (600, 333, 2, [12, 24, 36, 48, 100]), (1024, 50, 0, [20, 40]),
+                                       (13, 37, 0, [1, 3]), (23, 70, 2, [2, 5]), (201, 130, 1, [4, 8, 12, 16]),
+                                       (1023, 50, 0, [20, 40])])
 def test_global_test_matches_scipy(eng, N, P, r, ks):
     """Device F-tests (incomplete-beta continued fraction) against scipy's fdtrc through the
     host restatement of _minp_stats; includes strong signals (p down to ~1e-60)."""
