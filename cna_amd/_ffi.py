@@ -156,6 +156,8 @@ SIGNATURES = {
     'cna_x_columns': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
     'cna_gene_rank_corr_x': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 4
                              + [c_i64p, C.c_void_p]),
+    'cna_gene_rank_corr_x_by': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64]
+                                + [C.c_void_p] * 6),
     'cna_gene_rank_corr_wide': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 4 + [c_i64p, C.c_void_p]),
     'cna_x_generation': (C.c_int, [c_ctx, C.POINTER(C.c_int64)]),
     'cna_matrix_to_bins': (C.c_int, [c_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),

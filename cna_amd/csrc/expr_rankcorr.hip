@@ -133,26 +133,7 @@ __global__ __launch_bounds__(256) void k_rc_keyrank(const uint64_t* __restrict__
 // entries and the m cells they are ranked among: the gene's whole list (cna_gene_rank_corr) or, behind the sort's pass on
 // the level, the sub-segment of level blockIdx.y (cna_gene_rank_corr_by: k_l, m_l, z_l = m_l - k_l; a run cannot cross a
 // level because the list is one level's, and b sums to 0 over the level's kept cells, so the zero group's share holds).
-// Results go to [level][column][gene] and [level][gene].
-struct WholeGene {
-  const unsigned int* kept;
-  long long m;
-  __device__ __forceinline__ void operator()(int64_t g, int64_t, int, long long* at, long long* k, long long* cells) const {
-    *at = 0;
-    *k = (long long)kept[g];
-    *cells = m;
-  }
-};
-struct GeneLevel {
-  const unsigned int* dbase;          // [gene of the tile][digit] of the sort's last pass
-  const unsigned long long* mlev;     // kept cells per level
-  __device__ __forceinline__ void operator()(int64_t, int64_t in_tile, int level, long long* at, long long* k, long long* cells) const {
-    *at = (long long)dbase[in_tile * 256 + level];
-    *k = (long long)dbase[in_tile * 256 + level + 1] - *at;
-    *cells = (long long)mlev[level];
-  }
-};
-
+// Results go to [level][column][gene] and [level][gene].  (WholeGene and GeneLevel: rank_corr.h.)
 template <typename K, int W, class Src>
 __global__ __launch_bounds__(RS_UNIT) void k_rc_corr(const K* __restrict__ key, const uint32_t* __restrict__ cell,
                                                      const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,

@@ -1,6 +1,7 @@
-// cna_gene_rank_corr_x, cna_gene_rank_corr_wide, cna_x_columns: Spearman's rank correlation of every gene of the resident
-// expression matrix with up to 4096 per-cell columns from ONE sort of the matrix (cna.tl.gene_rank_test: the null of
-// cna.tl.gene_rank_corr under the association's permuted phenotypes, reference _association.py:94-99).  The null
+// cna_gene_rank_corr_x, cna_gene_rank_corr_x_by, cna_gene_rank_corr_wide, cna_x_columns: Spearman's rank correlation of
+// every gene of the resident expression matrix with up to 4096 per-cell columns from ONE sort of the matrix
+// (cna.tl.gene_rank_test: the null of cna.tl.gene_rank_corr under the association's permuted phenotypes, reference
+// _association.py:94-99).  The null
 // coefficient of permutation p is c_p = X z_p per cell (_association.py:99), and ranks are not linear in z_p: every c_p
 // is formed, ranked over the kept cells and correlated with every gene's ranks.  cna_gene_rank_corr (expr_rankcorr.hip)
 // takes 16 columns from the host and sorts the matrix on every call; here the columns are formed on the device from the
@@ -20,6 +21,13 @@
 //                         group is the slow grid index: the workgroups that run together gather from one table of 64 n bytes
 // Every sum is an integer: the results are those of cna_gene_rank_corr on each group of 16 columns under the same kept
 // set, integer for integer, whatever the tiling and on every run.
+//
+// cna_gene_rank_corr_x_by: the same inside every level of a clustering (cna.tl.gene_rank_test_strata), from the one sort
+// and one table per group.  k_rp_codes_by leaves a cell its level where it has a row of X (the level as a byte per cell,
+// the kept cells per level); rankcorr_keys ranks every group inside the levels; the genes' sort ends on its pass on the
+// level, and k_rp_rank runs once per (gene, level), k_rp_dot once per (gene, group, level), on the level's sub-segment
+// (GeneLevel of rank_corr.h, as k_rc_corr takes it) with the level's m_l, k_l and z_l.  Level l is cna_gene_rank_corr_x
+// with xrow set to -1 outside l, and each group of 16 columns cna_gene_rank_corr_by on them, integer for integer.
 #include "rank_corr.h"
 
 // hipcc contracts a*b+c into an fma by default.  cna_x_columns is specified as a product rounded on its own and THEN added
@@ -31,11 +39,31 @@ namespace {
 constexpr int RP_MAX_COLS = 4096;              // columns of one call
 constexpr int RP_MAX_SAMPLES = 1024;           // samples of X, as cna_expr_cross has it
 constexpr int RP_GROUP = RC_MAX_KEYS;          // columns of one table
+constexpr int RP_MAX_LEVELS = 255;             // cna_gene_rank_corr_x_by: the level is a digit of the sort, 255 = left out
 
 // codes[i] = 0 for a cell with a row of X, else -1: the kept cells as ranksum_sorted expects them
 __global__ __launch_bounds__(256) void k_rp_codes(const int64_t* __restrict__ xrow, int64_t n, int32_t* __restrict__ codes) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) codes[i] = xrow[i] >= 0 ? 0 : -1;
+}
+
+// cna_gene_rank_corr_x_by: codes holds the caller's levels, all in [-1, n_bins) with n_bins <= 255; a cell keeps its level
+// where it has a row of X, else -1; lvl8[i] = that level as a byte, 255 for -1 (the digit of the sort's last pass);
+// m[l] += the kept cells of level l (256 counters).  What k_rc_mask<true> does for finite columns
+__global__ __launch_bounds__(256) void k_rp_codes_by(const int64_t* __restrict__ xrow, int64_t n, int32_t* __restrict__ codes,
+                                                     uint8_t* __restrict__ lvl8, unsigned long long* __restrict__ m) {
+  __shared__ unsigned int h[256];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  if (i < n) {
+    const int32_t cd = xrow[i] >= 0 ? codes[i] : -1;
+    codes[i] = cd;
+    lvl8[i] = cd >= 0 ? (uint8_t)cd : (uint8_t)255;
+    if (cd >= 0) atomicAdd(&h[cd & 255], 1u);
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&m[threadIdx.x], (unsigned long long)h[threadIdx.x]);
 }
 
 // thread = cell i, blockIdx.y = 16 columns of the `cols` rows of Z (row-major, Nx each): out[j * n + i].  The row of Z is
@@ -73,24 +101,30 @@ __global__ __launch_bounds__(256) void k_rp_columns(const int64_t* __restrict__ 
   if (bad && !ok) atomicOr(bad, 1);
 }
 
-// workgroup = gene g0 + blockIdx.x over its kept[g] sorted entries {key, cell} among m kept cells, z = m - kept[g] implicit
+// workgroup = (gene g0 + blockIdx.x, level blockIdx.y) over the k sorted entries {key, cell} its source names (rank_corr.h:
+// the gene's whole list among m kept cells, or the sub-segment of the level among the level's m_l), z = m - k implicit
 // zeros.  a = s + e - m as k_rc_corr splits it: the walk forward stores s - m (+ z above the zero group), the walk backward
-// adds e (+ z from the zero group on) -- the same thread holds an entry in both.  a[] is indexed like the tile's entries.
-template <typename K>
+// adds e (+ z from the zero group on) -- the same thread holds an entry in both.  a[] is indexed like the tile's entries;
+// a_0 and the tie term go to [level][gene].  A list of no entry walks nothing, meets the fold's barriers and writes the
+// zero group alone: a_0 = 0 and its tie term.
+template <typename K, class Src>
 __global__ __launch_bounds__(RS_UNIT) void k_rp_rank(const K* __restrict__ key, const uint32_t* __restrict__ cell,
-                                                     const int64_t* __restrict__ seg, int64_t base, int64_t g0,
-                                                     const unsigned int* __restrict__ kept, long long m, int64_t n,
-                                                     int32_t* __restrict__ a, long long* __restrict__ a0,
+                                                     const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,
+                                                     Src src, int64_t n, int32_t* __restrict__ a, long long* __restrict__ a0,
                                                      double* __restrict__ tie) {
   constexpr K K0 = rs_key_zero<K>();
   __shared__ long long sh[RS_UNIT];
   __shared__ double tsh[RS_UNIT];
   __shared__ unsigned int below, zeros;
   const int64_t g = g0 + blockIdx.x;
-  const long long k = (long long)kept[g], z = m - k;
-  key += seg[g] - base;
-  cell += seg[g] - base;
-  a += seg[g] - base;
+  long long at, k, m;
+  src(g, (int64_t)blockIdx.x, (int)blockIdx.y, &at, &k, &m);
+  const long long z = m - k;
+  key += seg[g] - base + at;
+  cell += seg[g] - base + at;
+  a += seg[g] - base + at;
+  a0 += (int64_t)blockIdx.y * G;
+  tie += (int64_t)blockIdx.y * G;
   if (threadIdx.x == 0) below = zeros = 0;
   __syncthreads();
   RankWalkMine mine;
@@ -107,13 +141,15 @@ __global__ __launch_bounds__(RS_UNIT) void k_rp_rank(const K* __restrict__ key, 
   }
 }
 
-// workgroup = (gene g0 + blockIdx.x, group blockIdx.y): sum over the gene's stored kept entries of a x b[k] for the 16
-// columns of the group, k_rc_corr's accumulators (64 low bits and a 32-bit count of carries less borrows per thread and
-// column) and its fold; the zero group's share is -a_0 x (sum of b over the stored kept entries).  Column k of the call is
-// column k % 16 of group k / 16; the columns from q on are not stored.
+// workgroup = (gene g0 + blockIdx.x, group blockIdx.y, level blockIdx.z): sum over the stored kept entries its source names
+// (k_rp_rank's: the gene's, or those of the level's sub-segment) of a x b[k] for the 16 columns of the group, k_rc_corr's
+// accumulators (64 low bits and a 32-bit count of carries less borrows per thread and column) and its fold; the zero group's share is -a_0 x (sum of b over the stored kept entries).  Column k of the call is
+// column k % 16 of group k / 16; the columns from q on are not stored.  Results go to [level][column][gene].  The level
+// moves the pointers once, in front of the loop, which holds what it held.  A list of no entry writes zeros.
+template <class Src>
 __global__ __launch_bounds__(RS_UNIT) void k_rp_dot(const int32_t* __restrict__ a, const uint32_t* __restrict__ cell,
                                                     const int64_t* __restrict__ seg, int64_t base, int64_t g0, int64_t G,
-                                                    const unsigned int* __restrict__ kept, int64_t n, int q,
+                                                    Src src, int64_t n, int q,
                                                     const BRow<RP_GROUP>* __restrict__ btabs, const long long* __restrict__ a0,
                                                     unsigned long long* __restrict__ s_lo, long long* __restrict__ s_hi) {
   constexpr int W = RP_GROUP;
@@ -122,9 +158,13 @@ __global__ __launch_bounds__(RS_UNIT) void k_rp_dot(const int32_t* __restrict__ 
   const int t = threadIdx.x;
   const int64_t g = g0 + blockIdx.x;
   const int k0 = (int)blockIdx.y * W;
-  const long long k = (long long)kept[g];
-  a += seg[g] - base;
-  cell += seg[g] - base;
+  long long at, k, m;
+  src(g, (int64_t)blockIdx.x, (int)blockIdx.z, &at, &k, &m);
+  a += seg[g] - base + at;
+  cell += seg[g] - base + at;
+  a0 += (int64_t)blockIdx.z * G;
+  s_lo += (int64_t)blockIdx.z * q * G;
+  s_hi += (int64_t)blockIdx.z * q * G;
   const BRow<W>* __restrict__ btab = btabs + (int64_t)blockIdx.y * n;
   unsigned long long lo[W];
   int hi[W];
@@ -174,30 +214,47 @@ __global__ __launch_bounds__(RS_UNIT) void k_rp_dot(const int32_t* __restrict__ 
   }
 }
 
-// the genes' side: one sort of the matrix per tile of genes, the rank kernel and the dot kernel behind each
+// The levels of a call: one of all kept cells (lvl8 null: cna_gene_rank_corr_x, _wide), or the caller's (_x_by): the kept
+// cell's level as a byte in lvl8, the sort ending on its pass on the level, and the kept cells of every level on the
+// device (w->vm) and on the host (mlev)
+struct RankPermLevels {
+  int n_bins = 1;
+  const uint8_t* lvl8 = nullptr;
+  const unsigned long long* mlev = nullptr;
+};
+
+// the genes' side: one sort of the matrix per tile of genes, the rank kernel and the dot kernel behind each; with levels,
+// the rank kernel once per (gene, level) and the dot kernel once per (gene, group, level), each on the level's sub-segment
 template <typename T>
-int rankperm_genes(cna_ctx* c, ExprState* s, RankSumWork* w, const char* who, int q, int groups, int64_t m, int64_t work_bytes) {
+int rankperm_genes(cna_ctx* c, ExprState* s, RankSumWork* w, const char* who, int q, int groups, int64_t m, int64_t work_bytes,
+                   const RankPermLevels& lv) {
   using K = typename KeyOf<T>::K;
   const int64_t G = s->G, n = s->n;
   int rc = 0;
   CNA_TRY((ranksum_sorted<T, uint32_t>(
-      c, s, w, work_bytes, m, who, [&](const GeneTile& t, int64_t base, const K* key, const uint32_t* cell, const int64_t* seg) {
+      c, s, w, work_bytes, m, who,
+      [&](const GeneTile& t, int64_t base, const K* key, const uint32_t* cell, const int64_t* seg) {
         if (rc != 0) return;
         const unsigned genes = (unsigned)(t.g1 - t.g0);
         const int64_t entries = s->format == 1 ? (int64_t)genes * n : t.nch * s->chunk_len;   // of the tile, at most
         rc = buf_need(c, s->st, w->aent, 4 * std::max<int64_t>(1, entries));
         if (rc != 0) return;
-        {
-          ProfScope ps(c, CNA_K_RANKSUM_RANK, s->st);
-          hipLaunchKernelGGL((k_rp_rank<K>), dim3(genes), dim3(RS_UNIT), 0, s->st, key, cell, seg, base, t.g0,
-                             w->kept.as<const unsigned int>(), (long long)m, n, w->aent.as<int32_t>(), w->azero.as<long long>(),
-                             w->tie.as<double>());
-        }
-        ProfScope ps(c, CNA_K_RANKCORR_CORR, s->st);
-        hipLaunchKernelGGL(k_rp_dot, dim3(genes, (unsigned)groups), dim3(RS_UNIT), 0, s->st, w->aent.as<const int32_t>(), cell,
-                           seg, base, t.g0, G, w->kept.as<const unsigned int>(), n, q, w->btabs.as<const BRow<RP_GROUP>>(),
-                           w->azero.as<const long long>(), w->slo.as<unsigned long long>(), w->shi.as<long long>());
-      })));
+        const auto launch = [&](auto src) {
+          {
+            ProfScope ps(c, CNA_K_RANKSUM_RANK, s->st);
+            hipLaunchKernelGGL((k_rp_rank<K, decltype(src)>), dim3(genes, (unsigned)lv.n_bins), dim3(RS_UNIT), 0, s->st, key, cell,
+                               seg, base, t.g0, G, src, n, w->aent.as<int32_t>(), w->azero.as<long long>(), w->tie.as<double>());
+          }
+          ProfScope ps(c, CNA_K_RANKCORR_CORR, s->st);
+          hipLaunchKernelGGL((k_rp_dot<decltype(src)>), dim3(genes, (unsigned)groups, (unsigned)lv.n_bins), dim3(RS_UNIT), 0, s->st,
+                             w->aent.as<const int32_t>(), cell, seg, base, t.g0, G, src, n, q,
+                             w->btabs.as<const BRow<RP_GROUP>>(), w->azero.as<const long long>(),
+                             w->slo.as<unsigned long long>(), w->shi.as<long long>());
+        };
+        if (lv.lvl8) launch(GeneLevel{w->dbase.as<const unsigned int>(), w->vm.as<const unsigned long long>()});
+        else launch(WholeGene{w->kept.as<const unsigned int>(), (long long)m});
+      },
+      lv.lvl8)));
   return rc;
 }
 
@@ -209,23 +266,26 @@ struct RankPermOut {
   uint8_t* nan;
 };
 
-// What the two entries share behind their checks, with the kept cells in w->sort.code and their number m.  fill(k0, cols)
-// queues what puts the columns [k0, k0 + cols) of the call into w->vcol (cols x n); verdict() is asked once behind the last
-// group, before the matrix is sorted.  Every group's table and tie terms stay resident: 64 n bytes and 16 x 12 bytes each.
+// What the entries share behind their checks, with the kept cells in w->sort.code and their number m (over all levels).
+// fill(k0, cols) queues what puts the columns [k0, k0 + cols) of the call into w->vcol (cols x n); verdict() is asked once
+// behind the last group, before the matrix is sorted.  Every group's table and tie terms stay resident: 64 n bytes and, per
+// level, 16 x 12 bytes each (slot [group][level][column of the group], as rankcorr_keys lays a group's out).  Outputs per
+// level: s_lo, s_hi [n_bins, q, G], tie_gene [n_bins, G], tie_key [n_bins, q], m [n_bins].
 template <class Fill, class Verdict>
 int rankperm_core(cna_ctx* c, ExprState* s, RankSumWork* w, const char* who, int q, int64_t m, int64_t work_bytes, Fill&& fill,
-                  Verdict&& verdict, const RankPermOut& out) {
+                  Verdict&& verdict, const RankPermOut& out, const RankPermLevels& lv = {}) {
   const int64_t G = s->G, n = s->n;
   const int groups = (q + RP_GROUP - 1) / RP_GROUP;
-  const int64_t slots = (int64_t)groups * RP_GROUP;
-  const int64_t tab_bytes = 4 * (int64_t)RP_GROUP * n, tie_bytes = 12 * slots, s_bytes = 8 * (int64_t)q * G;
+  const int64_t group_slots = (int64_t)lv.n_bins * RP_GROUP, slots = groups * group_slots;
+  const int64_t tab_bytes = 4 * (int64_t)RP_GROUP * n, tie_bytes = 12 * slots;
+  const int64_t s_bytes = 8 * (int64_t)lv.n_bins * q * G, t_bytes = 8 * (int64_t)lv.n_bins * G;
   CNA_TRY(result_bufs_need(c, s->st, {{&w->vcol, 8 * (int64_t)RP_GROUP * n},
                                       {&w->btabs, tab_bytes * groups},
                                       {&w->tieks, tie_bytes},
                                       {&w->slo, s_bytes},
                                       {&w->shi, s_bytes},
-                                      {&w->tie, 8 * G},
-                                      {&w->azero, 8 * G}}));
+                                      {&w->tie, t_bytes},
+                                      {&w->azero, t_bytes}}));
   unsigned long long* tie_lo = w->tieks.as<unsigned long long>();          // [slot] 64 low bits, then [slot] 32 high bits
   unsigned int* tie_hi = w->tieks.as<unsigned int>() + 2 * slots;
   {
@@ -238,27 +298,31 @@ int rankperm_core(cna_ctx* c, ExprState* s, RankSumWork* w, const char* who, int
   for (int gi = 0; gi < groups; ++gi) {
     const int k0 = gi * RP_GROUP, cols = std::min(RP_GROUP, q - k0);
     CNA_TRY(fill(k0, cols));
-    CNA_TRY(rankcorr_keys(c, s, w, cols, RP_GROUP, work_bytes, m, nullptr, w->btabs.as<int32_t>() + (int64_t)k0 * n, tie_lo + k0,
-                          tie_hi + k0, who));
+    CNA_TRY(rankcorr_keys(c, s, w, cols, RP_GROUP, work_bytes, m, lv.lvl8, w->btabs.as<int32_t>() + (int64_t)k0 * n,
+                          tie_lo + gi * group_slots, tie_hi + gi * group_slots, who));
   }
   CNA_TRY(verdict());
-  if (s->is_f64) CNA_TRY(rankperm_genes<double>(c, s, w, who, q, groups, m, work_bytes));
-  else CNA_TRY(rankperm_genes<float>(c, s, w, who, q, groups, m, work_bytes));
+  if (s->is_f64) CNA_TRY(rankperm_genes<double>(c, s, w, who, q, groups, m, work_bytes, lv));
+  else CNA_TRY(rankperm_genes<float>(c, s, w, who, q, groups, m, work_bytes, lv));
   std::vector<unsigned int> nanf((size_t)G);
   std::vector<unsigned long long> tie_words((size_t)(tie_bytes / 8) + 1);
   {
     ProfScope ps(c, CNA_K_RANKSUM_FETCH, s->st);
     CNA_TRY(fetch_results(s->st, who, {{out.s_lo, w->slo.p, (size_t)s_bytes},
                                        {out.s_hi, w->shi.p, (size_t)s_bytes},
-                                       {out.tie_gene, w->tie.p, (size_t)(8 * G)},
+                                       {out.tie_gene, w->tie.p, (size_t)t_bytes},
                                        {tie_words.data(), w->tieks.p, (size_t)tie_bytes},
                                        {nanf.data(), w->nanf.p, (size_t)(4 * G)}}));
   }
   for (int64_t g = 0; g < G; ++g) out.nan[g] = nanf[(size_t)g] ? 1 : 0;
   const unsigned int* tie_high = reinterpret_cast<const unsigned int*>(tie_words.data() + slots);
-  for (int k = 0; k < q; ++k)                           // rounded once
-    out.tie_key[k] = (double)tie_high[k] * 18446744073709551616.0 + (double)tie_words[(size_t)k];
-  *out.m = m;
+  for (int l = 0; l < lv.n_bins; ++l) {
+    for (int k = 0; k < q; ++k) {                       // rounded once
+      const size_t slot = (size_t)((k / RP_GROUP) * group_slots + (int64_t)l * RP_GROUP + k % RP_GROUP);
+      out.tie_key[(int64_t)l * q + k] = (double)tie_high[slot] * 18446744073709551616.0 + (double)tie_words[slot];
+    }
+    out.m[l] = lv.mlev ? (int64_t)lv.mlev[l] : m;
+  }
   return 0;
 }
 
@@ -292,6 +356,32 @@ int x_entry(cna_ctx* c, const char* who, const int64_t* xrow, int64_t n_cells, c
   return 0;
 }
 
+// What cna_gene_rank_corr_x and cna_gene_rank_corr_x_by share behind x_entry, with the kept cells in w->sort.code: the
+// columns formed from X group by group, the verdict on what was formed, the core
+int rankperm_x(cna_ctx* c, ExprState* s, RankSumWork* w, const char* who, int q, int64_t m, int64_t work_bytes,
+               const RankPermOut& out, const RankPermLevels& lv) {
+  const int64_t n = s->n;
+  const dim3 cells((unsigned)((n + 255) / 256));
+  CNA_TRY(buf_need(c, s->st, w->vcol, 8 * (int64_t)RP_GROUP * n));
+  int* bad = w->xflag.as<int>() + 8;                   // (behind xrow_check's verdict and count)
+  HIP_TRY(hipMemsetAsync(bad, 0, 4, s->st));
+  const auto fill = [&](int k0, int cols) {
+    ProfScope ps(c, CNA_K_RANKCORR_KEYS, s->st);
+    hipLaunchKernelGGL(k_rp_columns, cells, dim3(256), 0, s->st, w->xrow.as<const int64_t>(), n, (const double*)c->X, c->ldx, c->Nx,
+                       w->zrows.as<const double>() + (int64_t)k0 * c->Nx, cols, w->vcol.as<double>(), bad);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
+  const auto verdict = [&]() {
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, bad, 4, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+    if (flag) CNA_FAIL(CNA_EINVAL, std::string(who) + ": a formed value X[xrow[i]] . Z[j] is not finite (an inf or a NaN in X or in Z)");
+    return 0;
+  };
+  return rankperm_core(c, s, w, who, q, m, work_bytes, fill, verdict, out, lv);
+}
+
 }  // namespace
 
 extern "C" int cna_x_columns(cna_ctx* c, const int64_t* xrow, int64_t n_cells, const double* Z, int q, double* out) {
@@ -323,27 +413,44 @@ extern "C" int cna_gene_rank_corr_x(cna_ctx* c, const int64_t* xrow, int64_t n_c
   int64_t m = 0;
   CNA_TRY(x_entry(c, who, xrow, n_cells, Z, q, !s_lo || !s_hi || !tie_gene || !tie_key || !m_out || !nan_out, &s, &w, &m));
   const int64_t n = s->n;
-  const dim3 cells((unsigned)((n + 255) / 256));
   CNA_TRY(buf_need(c, s->st, w->sort.code, 4 * n));
-  CNA_TRY(buf_need(c, s->st, w->vcol, 8 * (int64_t)RP_GROUP * n));
-  int* bad = w->xflag.as<int>() + 8;                   // (behind xrow_check's verdict and count)
-  HIP_TRY(hipMemsetAsync(bad, 0, 4, s->st));
-  hipLaunchKernelGGL(k_rp_codes, cells, dim3(256), 0, s->st, w->xrow.as<const int64_t>(), n, w->sort.code.as<int32_t>());
-  const auto fill = [&](int k0, int cols) {
+  hipLaunchKernelGGL(k_rp_codes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, w->xrow.as<const int64_t>(), n,
+                     w->sort.code.as<int32_t>());
+  return rankperm_x(c, s, w, who, q, m, work_bytes, {s_lo, s_hi, tie_gene, tie_key, m_out, nan_out}, {});
+}
+
+extern "C" int cna_gene_rank_corr_x_by(cna_ctx* c, const int64_t* xrow, int64_t n_cells, const double* Z, int q,
+                                       const int32_t* codes, int n_bins, int64_t work_bytes, uint64_t* s_lo, int64_t* s_hi,
+                                       double* tie_gene, double* tie_key, int64_t* m_out, uint8_t* nan_out) {
+  CHECK_CTX(c);
+  const char* who = "cna_gene_rank_corr_x_by";
+  if (work_bytes < 0) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr_x_by: work_bytes is 0 (the default) or a number of bytes");
+  ExprState* s = nullptr;
+  RankSumWork* w = nullptr;
+  int64_t with_row = 0;
+  CNA_TRY(x_entry(c, who, xrow, n_cells, Z, q, !codes || !s_lo || !s_hi || !tie_gene || !tie_key || !m_out || !nan_out, &s, &w,
+                  &with_row));
+  if (n_bins < 1 || n_bins > RP_MAX_LEVELS) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr_x_by: 1 <= n_bins <= 255");
+  const int64_t n = s->n;
+  // the caller's codes into w->sort.code, judged; then a cell keeps its level where it has a row of X
+  CNA_TRY(sort_count(c, s->st, w->sort, CellListOf<256>{}, codes, n, n_bins, 0, 2,
+                     "cna_gene_rank_corr_x_by: a code lies outside [-1, n_bins)"));
+  CNA_TRY(buf_need(c, s->st, w->lvl8, n));
+  CNA_TRY(buf_need(c, s->st, w->vm, 8 * 256));
+  std::vector<unsigned long long> mlev((size_t)n_bins);
+  {
     ProfScope ps(c, CNA_K_RANKCORR_KEYS, s->st);
-    hipLaunchKernelGGL(k_rp_columns, cells, dim3(256), 0, s->st, w->xrow.as<const int64_t>(), n, (const double*)c->X, c->ldx, c->Nx,
-                       w->zrows.as<const double>() + (int64_t)k0 * c->Nx, cols, w->vcol.as<double>(), bad);
+    HIP_TRY(hipMemsetAsync(w->vm.p, 0, 8 * 256, s->st));
+    hipLaunchKernelGGL(k_rp_codes_by, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->st, w->xrow.as<const int64_t>(), n,
+                       w->sort.code.as<int32_t>(), w->lvl8.as<uint8_t>(), w->vm.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
-    return 0;
-  };
-  const auto verdict = [&]() {
-    int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, bad, 4, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipMemcpyAsync(mlev.data(), w->vm.p, 8 * (size_t)n_bins, hipMemcpyDeviceToHost, s->st));
     HIP_TRY(hipStreamSynchronize(s->st));
-    if (flag) CNA_FAIL(CNA_EINVAL, "cna_gene_rank_corr_x: a formed value X[xrow[i]] . Z[j] is not finite (an inf or a NaN in X or in Z)");
-    return 0;
-  };
-  return rankperm_core(c, s, w, who, q, m, work_bytes, fill, verdict, {s_lo, s_hi, tie_gene, tie_key, m_out, nan_out});
+  }
+  int64_t m = 0;
+  for (int b = 0; b < n_bins; ++b) m += (int64_t)mlev[(size_t)b];
+  return rankperm_x(c, s, w, who, q, m, work_bytes, {s_lo, s_hi, tie_gene, tie_key, m_out, nan_out},
+                    {n_bins, w->lvl8.as<const uint8_t>(), mlev.data()});
 }
 
 extern "C" int cna_gene_rank_corr_wide(cna_ctx* c, const double* V, int q, int64_t work_bytes, uint64_t* s_lo, int64_t* s_hi,

@@ -1,6 +1,7 @@
 // Private to expr_rankcorr.hip (cna_gene_rank_corr, cna_gene_rank_corr_by) and expr_rankperm.hip (cna_gene_rank_corr_x,
-// cna_gene_rank_corr_wide): what the two files share of the columns' side of Spearman's rho -- the kept cells of a set of
-// columns, the ranks of up to 16 columns as a cell-major table, and the shape of one row of that table.  One statement of
+// cna_gene_rank_corr_x_by, cna_gene_rank_corr_wide): what the two files share of Spearman's rho -- the kept cells of a set
+// of columns, the ranks of up to 16 columns as a cell-major table, the shape of one row of that table, and what list of a
+// gene a workgroup behind the genes' sort walks (the whole gene, or one level of it).  One statement of
 // each: the kernels behind rankcorr_keys (k_rc_vkeys, k_rc_keyrank) stay where it is defined, expr_rankcorr.hip.
 #pragma once
 #include "rank_sort.h"
@@ -43,6 +44,29 @@ __global__ __launch_bounds__(256) void k_rc_mask(const double* __restrict__ V, i
 template <int W>
 struct alignas(4 * W) BRow {
   int32_t v[W];
+};
+
+// What a workgroup behind the genes' sort walks (k_rc_corr; k_rp_rank and k_rp_dot of expr_rankperm.hip): where its list
+// begins inside the gene's segment (at), its k stored kept entries and the cells they are ranked among.  src(gene, gene's
+// index in the tile, level, &at, &k, &cells).  WholeGene: the gene's whole list, level 0 only.  GeneLevel: behind the
+// sort's pass on the level, the sub-segment of that level with the level's kept cells; an empty level gives k = 0.
+struct WholeGene {
+  const unsigned int* kept;
+  long long m;
+  __device__ __forceinline__ void operator()(int64_t g, int64_t, int, long long* at, long long* k, long long* cells) const {
+    *at = 0;
+    *k = (long long)kept[g];
+    *cells = m;
+  }
+};
+struct GeneLevel {
+  const unsigned int* dbase;          // [gene of the tile][digit] of the sort's last pass
+  const unsigned long long* mlev;     // kept cells per level
+  __device__ __forceinline__ void operator()(int64_t, int64_t in_tile, int level, long long* at, long long* k, long long* cells) const {
+    *at = (long long)dbase[in_tile * 256 + level];
+    *k = (long long)dbase[in_tile * 256 + level + 1] - *at;
+    *cells = (long long)mlev[level];
+  }
 };
 
 // The ranks of the q <= 16 columns in w->vcol (q x n float64) over the m kept cells of w->sort.code: tiles of whole columns

@@ -41,8 +41,9 @@ struct RankSumWork : BufSet {
   // cna_gene_rank_corr: the columns, the kept cells' count, b[cell][W], the columns' tie terms (96 bits), the two limbs of S
   Buf vcol{*this}, vm{*this}, btab{*this}, tiek{*this}, slo{*this}, shi{*this};
   Buf lvl8{*this};                                                     // cna_gene_rank_corr_by: the kept cell's level as a byte
-  // cna_gene_rank_corr_x / _wide (expr_rankperm.hip): the tables b[group][cell][16] and the tie terms of every group of 16
-  // columns; a = s + e - m of every entry of a tile of genes and a_0 of every gene; xrow with its verdict, Z, the columns
+  // cna_gene_rank_corr_x / _x_by / _wide (expr_rankperm.hip): the tables b[group][cell][16] and the tie terms of every group
+  // of 16 columns (per level in _x_by); a = s + e - m of every entry of a tile of genes and a_0 of every (level, gene); xrow
+  // with its verdict, Z, the columns.  _x_by adds no buffer: its levels ride in lvl8 and vm, as cna_gene_rank_corr_by's
   Buf btabs{*this}, tieks{*this}, aent{*this}, azero{*this}, xrow{*this}, xseen{*this}, xflag{*this}, zrows{*this}, xcols{*this};
   // cna_gene_ranksum_within (its blocks ride in lvl8): the weights and the sizes of its (block, level) table; the results
   Buf wtab{*this}, wd2{*this}, wnum{*this}, wtiew{*this}, wlive{*this};

@@ -14,6 +14,10 @@ import scipy.sparse as sp
 from . import _ffi, _order
 from ._ffi import check, ptr, MAT_NAM, MAT_X
 
+# the integer results (s_lo, s_hi) one cna_gene_rank_corr_x_by call may return: Engine.gene_rank_corr_x_by takes its columns in
+# chunks within it.  The figure of Engine.CROSS_BY_HOST_BYTES; a module constant so that a test can lower it
+RANK_X_BY_HOST_BYTES = 1 << 30
+
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
@@ -1485,6 +1489,43 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_gene_rank_corr_x(self.h, ptr(xrow), len(xrow), ptr(Z), q, int(work_bytes), ptr(s_lo), ptr(s_hi),
                                             ptr(tie_gene), ptr(tie_key), C.byref(m), ptr(nan)), 'cna_gene_rank_corr_x')
         return s_lo, s_hi, tie_gene, tie_key, int(m.value), nan.astype(bool)
+
+    def gene_rank_corr_x_by(self, xrow, Z, codes, n_levels, work_bytes=0):
+        """`gene_rank_corr_x` inside every level of `codes` (int32 per cell, -1 = cell left out, at most 255 levels) from
+        one sort of the resident matrix per library call (cna_gene_rank_corr_x_by): level l is ranked over its cells with
+        xrow[i] >= 0, m[l] of them.  Returns (s_lo uint64[L, q, genes], s_hi int64[L, q, genes], tie_gene float64[L, genes],
+        tie_key float64[L, q], m int64[L], nan bool[genes]); level l's slices are what `gene_rank_corr_x` returns for xrow
+        set to -1 outside the level, and every group of 16 columns what `gene_rank_corr_by` returns for those rows of
+        `x_columns(xrow, Z)`.  The integers take 16 L q genes bytes: the rows of Z go in chunks of whole groups of 16 whose
+        results stay within RANK_X_BY_HOST_BYTES (one group at least) and the chunks are concatenated -- a group's
+        integers depend on xrow, codes and its own 16 rows alone, so the chunking changes no bit.  One rank, replicated
+        view.  No memo."""
+        xrow, Z, q, info = self._x_columns_args(xrow, Z, 'gene_rank_corr_x_by')
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if info['format'] != 'none' and codes.shape != xrow.shape:
+            raise ValueError('gene_rank_corr_x_by: %d codes for %d resident cells' % (codes.size, info['n_cells']))
+        L, G = max(int(n_levels), 0), info['n_genes']
+        s_lo = np.empty((L, max(q, 0), G), dtype=np.uint64)
+        s_hi = np.empty((L, max(q, 0), G), dtype=np.int64)
+        tie_gene, tie_key = np.empty((L, G)), np.empty((L, max(q, 0)))
+        m, nan = np.empty(L, dtype=np.int64), np.empty(G, dtype=np.uint8)
+
+        def call(Zc, lo, hi, tk):
+            check(self.lib.cna_gene_rank_corr_x_by(self.h, ptr(xrow), len(xrow), ptr(Zc), int(Zc.shape[0]) if Zc.ndim == 2 else 0,
+                                                   ptr(codes), int(n_levels), int(work_bytes), ptr(lo), ptr(hi), ptr(tie_gene),
+                                                   ptr(tk), ptr(m), ptr(nan)), 'cna_gene_rank_corr_x_by')
+
+        step = 16 * max(1, int(RANK_X_BY_HOST_BYTES) // max(1, 16 * 16 * L * G))      # columns of one call
+        if q <= step or q > 4096:
+            call(Z, s_lo, s_hi, tie_key)                       # (and every q the library refuses: the refusal is the library's)
+        else:
+            for k0 in range(0, q, step):                       # tie_gene, m and nan are every chunk's alike
+                cols = min(step, q - k0)
+                lo, hi = np.empty((L, cols, G), dtype=np.uint64), np.empty((L, cols, G), dtype=np.int64)
+                tk = np.empty((L, cols))
+                call(np.ascontiguousarray(Z[k0:k0 + cols]), lo, hi, tk)
+                s_lo[:, k0:k0 + cols], s_hi[:, k0:k0 + cols], tie_key[:, k0:k0 + cols] = lo, hi, tk
+        return s_lo, s_hi, tie_gene, tie_key, m, nan.astype(bool)
 
     def gene_rank_corr_wide(self, V, work_bytes=0):
         """`gene_rank_corr` for 1 <= q <= 4096 rows of V (q x cells float64) from one sort of the resident matrix

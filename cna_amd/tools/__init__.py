@@ -11,6 +11,7 @@ from ._gene_test_strata import gene_test_strata
 from ._gene_markers import gene_markers, gene_markers_pairs, gene_markers_within
 from ._gene_rank_corr import gene_rank_corr, gene_rank_corr_strata
 from ._gene_rank_perm import gene_rank_test
+from ._gene_rank_perm_strata import gene_rank_test_strata
 from ._nam_strata import nam_strata
 from ._gene_sets import gene_set_enrich, gene_set_test
 
@@ -27,6 +28,7 @@ __all__ = [
     'gene_rank_corr',
     'gene_rank_corr_strata',
     'gene_rank_test',
+    'gene_rank_test_strata',
     'gene_set_enrich',
     'gene_set_test',
     'gene_test',

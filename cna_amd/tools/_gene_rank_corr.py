@@ -126,7 +126,7 @@ def gene_rank_corr_strata(data, stratification, keys='coef', layer=None, engine=
     levels (an Index named after the stratification) for a ``str`` key, a MultiIndex ``(key, level)``, key-major, for a
     list of keys.
 
-    Not here: p-values (as in ``gene_rank_corr``), a pooled "within" coefficient across the levels (ranks inside different
+    p-values: ``gene_rank_test_strata``, a permutation null per level.  Not here: a pooled "within" coefficient across the levels (ranks inside different
     levels do not pool the way ``gene_corr_strata``'s centred sums do), more than 255 levels or 16 keys per call, sharded
     data."""
     engine = engine or get_engine()

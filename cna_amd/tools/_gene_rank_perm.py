@@ -27,6 +27,19 @@ from ._genes import expression_of, gene_index, key_columns
 from ._nam import refuse_sharded
 
 
+def checked_n_perm(n_perm, who):
+    """None, or n_perm as an int >= 1 (``gene_rank_test`` and ``gene_rank_test_strata``: the cost is linear in it)"""
+    if n_perm is None:
+        return None
+    try:
+        n_perm = operator.index(None if isinstance(n_perm, (bool, np.bool_)) else n_perm)
+    except TypeError:
+        raise TypeError('%s: n_perm must be an integer >= 1 or None, got %r' % (who, n_perm)) from None
+    if n_perm < 1:
+        raise ValueError('%s: n_perm must be an integer >= 1 or None, got %r' % (who, n_perm))
+    return n_perm
+
+
 def gene_rank_test(data, y, sid_name, batches=None, covs=None, donorids=None, layer=None, key_added='coef', var_key_added=None,
                    n_perm=None, return_null=False, engine=None, **kwargs):
     """``association(data, y, sid_name, batches, covs, donorids, key_added=key_added, **kwargs)`` and, for every gene of
@@ -53,16 +66,10 @@ def gene_rank_test(data, y, sid_name, batches=None, covs=None, donorids=None, la
     The kept cells of rho are those where the stored coefficient is finite, the kept cells of the null those with a row in
     X: the same cells, and a RuntimeError if the two calls ever disagree on their number.
 
-    Not here: sharded data, a version inside the levels of a clustering, Kendall's tau."""
+    Inside the levels of a clustering: ``gene_rank_test_strata``.  Not here: sharded data, Kendall's tau."""
     engine = engine or get_engine()
     refuse_sharded(data, engine, 'gene_rank_test', 'the ranking runs over all cells of a gene: the rows of other ranks are elsewhere')
-    if n_perm is not None:
-        try:
-            n_perm = operator.index(None if isinstance(n_perm, (bool, np.bool_)) else n_perm)
-        except TypeError:
-            raise TypeError('gene_rank_test: n_perm must be an integer >= 1 or None, got %r' % (n_perm,)) from None
-        if n_perm < 1:
-            raise ValueError('gene_rank_test: n_perm must be an integer >= 1 or None, got %r' % (n_perm,))
+    n_perm = checked_n_perm(n_perm, 'gene_rank_test')
     X = expression_of(data, layer, 'gene_rank_test')
     res, Zall, P = null_phenotypes(data, y, sid_name, batches, covs, donorids, key_added, engine, kwargs, 'gene_rank_test')
     if n_perm is not None:

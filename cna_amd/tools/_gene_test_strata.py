@@ -51,10 +51,10 @@ def level_statistics(sums, Zall, constant):
     return table, null_r
 
 
-def strata_frame(table, levels, stratification, gindex):
-    """genes x MultiIndex (level, statistic), level-major"""
+def strata_frame(table, levels, stratification, gindex, statistics=STATISTICS):
+    """genes x MultiIndex (level, statistic), level-major; `statistics` names the table's second axis"""
     L, S, G = table.shape
-    columns = pd.MultiIndex.from_product([pd.Index(levels, name=stratification), STATISTICS],
+    columns = pd.MultiIndex.from_product([pd.Index(levels, name=stratification), list(statistics)],
                                          names=[stratification, 'statistic'])
     return pd.DataFrame(np.ascontiguousarray(table.reshape(L * S, G).T), index=gindex, columns=columns)
 

@@ -85,7 +85,7 @@ enum {
   CNA_K_RANKSUM_PAIRS,
   /* cna_gene_rank_corr: the ranks of the columns (their upload, the kept cells, the kernel behind their sort) and the
    * correlation kernel behind the genes' sort; the keys, both sorts and the copies back are counted under
-   * CNA_K_RANKSUM_KEYS, _SORT and _FETCH.  cna_gene_rank_corr_x / _wide (and cna_x_columns): the kernel that forms the
+   * CNA_K_RANKSUM_KEYS, _SORT and _FETCH.  cna_gene_rank_corr_x / _x_by / _wide (and cna_x_columns): the kernel that forms the
    * columns from X, or their upload, under CNA_K_RANKCORR_KEYS beside the ranks; the kernel that stores a per entry under
    * CNA_K_RANKSUM_RANK; the dot kernel under CNA_K_RANKCORR_CORR */
   CNA_K_RANKCORR_KEYS, CNA_K_RANKCORR_CORR,
@@ -924,6 +924,28 @@ int  cna_x_columns(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, const dou
 int  cna_gene_rank_corr_x(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, const double* Z, int q, int64_t work_bytes,
                           uint64_t* s_lo_out, int64_t* s_hi_out, double* tie_gene_out, double* tie_key_out, int64_t* m_out,
                           uint8_t* nan_out);
+/* cna.tl.gene_rank_test_strata: cna_gene_rank_corr_x inside every level of a clustering, from the ONE sort of the matrix
+ * and one table per group of 16 columns.  1 <= q <= 4096, 1 <= n_bins <= 255.
+ *   codes[i]  the level of cell i in [0, n_bins), or -1: the cell is left out (judged as cna_gene_rank_corr_by judges them)
+ * The kept cells of level l, C_l, are the cells with codes[i] == l and xrow[i] >= 0; genes and columns are ranked with
+ * midranks inside C_l.
+ *   s_lo_out, s_hi_out [(l * q + k) * n_genes + g]   S of level l, column k, gene g
+ *   tie_gene_out[l * n_genes + g], tie_key_out[l * q + k]   the tie terms inside C_l
+ *   m_out[l] = |C_l|
+ *   nan_out[g]  a cell of ANY C_l holds NaN in gene g: cna_gene_rank_corr_by's guard on the whole gene (its other outputs
+ *             are unspecified in every level)
+ * Level l equals cna_gene_rank_corr_x called with xrow set to -1 outside level l, and every group of 16 columns equals
+ * cna_gene_rank_corr_by on those columns of cna_x_columns(xrow, Z) under the same codes: integer for integer (s_lo, s_hi,
+ * both tie terms and m), under every work_bytes and on every run.  A cell keeps its level where it has a row of X; every
+ * group is ranked inside the levels (cna_gene_rank_corr_by's searches) with n_bins x 16 tie terms of its own; the genes'
+ * sort ends on its pass on the level, the kernel that stores a runs once per (gene, level) on the level's sub-segment with
+ * m_l cells, k_l stored entries and m_l - k_l implicit zeros, and the dot kernel once per (gene, group, level).  An empty
+ * (gene, level) gives S = 0.  The results take 16 x n_bins x q x n_genes bytes on the device and on the host.
+ * CNA_ESTATE, CNA_EINVAL as cna_gene_rank_corr_x; CNA_EINVAL, with nothing written, also for n_bins outside [1, 255] and a
+ * code outside [-1, n_bins).  CNA_ENOMEM: the tables or the results do not fit. */
+int  cna_gene_rank_corr_x_by(cna_ctx* ctx, const int64_t* xrow, int64_t n_cells, const double* Z, int q, const int32_t* codes,
+                             int n_bins, int64_t work_bytes, uint64_t* s_lo_out, int64_t* s_hi_out, double* tie_gene_out,
+                             double* tie_key_out, int64_t* m_out, uint8_t* nan_out);
 /* The same core with the columns given by the host: V[k * n_cells + i], 1 <= q <= 4096.  The kept cells are those where
  * EVERY one of the q columns is finite: one set per call, as in cna_gene_rank_corr, found in a first pass over V before
  * any column is ranked.  Needs no X and no graph.  CNA_ESTATE: no expression matrix is resident.  CNA_EINVAL: a null
