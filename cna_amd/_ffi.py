@@ -171,6 +171,8 @@ SIGNATURES = {
     'cna_graph_components_find': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cna_graph_components_list': (C.c_int, [c_ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cna_graph_components_label': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    'cna_nbhd_expr': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'cna_gene_nbhd_corr': (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
 }
 
 MAT_NAM, MAT_X, MAT_PROJ = 0, 1, 2

@@ -9,7 +9,9 @@
 // cna_gene_rank_corr_by (expr_rankcorr.hip: Spearman's rho against per-cell columns from the same ranking) and
 // cna_gene_rank_corr_x, cna_gene_rank_corr_wide and cna_x_columns (expr_rankperm.hip: rho against up to 4096 columns, formed
 // from X or given, from one sort), the three files sharing rank_sort.h: a
-// radix sort on the chunk tables, the walk over a sorted list and their buffers.  What two of them need is here once:
+// radix sort on the chunk tables, the walk over a sorted list and their buffers; cna_nbhd_expr and cna_gene_nbhd_corr
+// (expr_nbhd.hip: the random walk over tiles of gene columns, reading the resident graph as components.hip does).  What two
+// of them need is here once:
 //   Buf / BufSet    grow-only device buffers that are freed by having been declared
 //   ExprState       the resident matrix, the stream, and one slot of work buffers per entry point
 //   sort_*          the counting sort of the cells by code (cell list of cna_expr_to_bins and cna_gene_corr_by, value
@@ -17,6 +19,7 @@
 //   gene_tiles      the walk over tiles of whole genes of the gene-major kernels
 //   xrow_check      the verdict on a map cells -> rows of X (cna_expr_cross, the two entries by level, the two of
 //                   expr_rankperm.hip that read X)
+//   k_key_stats     the statistics of per-cell key columns (cna_gene_corr, cna_gene_nbhd_corr)
 //   with_bool / with_width, fetch_results, result_bufs_need, finite_d, wave_min / wave_max
 // Templates are instantiated where they are used; nothing here needs relocatable device code.
 #pragma once
@@ -61,7 +64,7 @@ struct ScopedBufs : BufSet {
 
 // ------------------------------------------------------------------ state (cna_ctx::expr)
 enum ExprUser { EXPR_CORR, EXPR_BINS, EXPR_CROSS, EXPR_STRATA, EXPR_CORR_BY, EXPR_MAT_BINS, EXPR_ENRICH, EXPR_CROSS_BY,
-                EXPR_GRAM_BY, EXPR_RASTER, EXPR_COMPONENTS, EXPR_RANKSUM, EXPR_USERS };
+                EXPR_GRAM_BY, EXPR_RASTER, EXPR_COMPONENTS, EXPR_RANKSUM, EXPR_NBHD, EXPR_USERS };
 
 struct ExprState {
   hipStream_t st = nullptr;
@@ -148,6 +151,62 @@ __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// ------------------------------------------------------------------ statistics of per-cell key columns
+// (cna_gene_corr, cna_gene_nbhd_corr)
+constexpr int KS_LD = 8;   // doubles per key in the key statistics block: n, mean, sum vc^2, sum vc, min, max
+// one block of 1024 threads per key: thread t adds the cells t, t + 1024, ...; the 1024 partial sums are folded by a
+// fixed tree -- the same bits on every run
+static __global__ __launch_bounds__(1024) void k_key_stats(const double* __restrict__ V, int64_t n, double* __restrict__ ks) {
+  __shared__ double sh[4][1024];
+  const int j = blockIdx.x, t = threadIdx.x;
+  const double* v = V + (int64_t)j * n;
+  double cnt = 0, sum = 0, mn = INFINITY, mx = -INFINITY;
+  for (int64_t i = t; i < n; i += 1024) {
+    const double x = v[i];
+    if (finite_d(x)) {
+      cnt += 1.0;
+      sum += x;
+      mn = fmin(mn, x);
+      mx = fmax(mx, x);
+    }
+  }
+  sh[0][t] = cnt; sh[1][t] = sum; sh[2][t] = mn; sh[3][t] = mx;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if (t < w) {
+      sh[0][t] += sh[0][t + w];
+      sh[1][t] += sh[1][t + w];
+      sh[2][t] = fmin(sh[2][t], sh[2][t + w]);
+      sh[3][t] = fmax(sh[3][t], sh[3][t + w]);
+    }
+    __syncthreads();
+  }
+  const double N = sh[0][0], mean = N > 0 ? sh[1][0] / N : 0.0, vmin = sh[2][0], vmax = sh[3][0];
+  __syncthreads();
+  double s1 = 0, s2 = 0;
+  for (int64_t i = t; i < n; i += 1024) {
+    const double x = v[i];
+    if (finite_d(x)) {
+      const double d = x - mean;
+      s1 += d;
+      s2 += d * d;
+    }
+  }
+  sh[0][t] = s1; sh[1][t] = s2;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if (t < w) {
+      sh[0][t] += sh[0][t + w];
+      sh[1][t] += sh[1][t + w];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    double* o = ks + j * KS_LD;
+    o[0] = N; o[1] = mean; o[2] = sh[1][0]; o[3] = sh[0][0]; o[4] = vmin; o[5] = vmax; o[6] = 0; o[7] = 0;
+  }
 }
 
 // ------------------------------------------------------------------ counting sort of the cells by code

@@ -4,7 +4,7 @@
 //     d.var['corr_case'] = np.corrcoef(d.obs.male_coef.values.reshape(1,-1), d.X, rowvar=False)[0,1:]
 // The key columns are in the CALLER's cell order, as the matrix is.
 //
-//   k_key_stats     per key column: finite count, mean, sum (v - mean), sum (v - mean)^2, min, max (fixed-order sums)
+//   k_key_stats     (expr.h) per key column: finite count, mean, sum (v - mean), sum (v - mean)^2, min, max (fixed-order sums)
 //   k_key_table     cells x Q table of centred key values (0 where the cell is left out) + one mask word per cell
 //   k_gc_dense      X is cells x genes: lane = gene, a wave walks down a slab of cells (coalesced rows, the key values
 //                   of a cell are wave-uniform); partial sums per slab with plain stores
@@ -19,67 +19,13 @@
 namespace {
 
 constexpr int GC_MAXQ = 16;
-constexpr int KS_LD = 8;   // doubles per key in the key statistics block: n, mean, sum vc^2, sum vc, min, max
 
 // raw key columns, their table and masks, the key statistics, the partial records, r, the "masks differ" word
 struct CorrWork : BufSet {
   Buf vraw{*this}, vtab{*this}, vmask{*this}, kstat{*this}, part{*this}, rout{*this}, flag{*this};
 };
 
-// ------------------------------------------------------------------ key columns
-// one block of 1024 threads per key: thread t adds the cells t, t + 1024, ...; the 1024 partial sums are folded by a
-// fixed tree -- the same bits on every run
-__global__ __launch_bounds__(1024) void k_key_stats(const double* __restrict__ V, int64_t n, double* __restrict__ ks) {
-  __shared__ double sh[4][1024];
-  const int j = blockIdx.x, t = threadIdx.x;
-  const double* v = V + (int64_t)j * n;
-  double cnt = 0, sum = 0, mn = INFINITY, mx = -INFINITY;
-  for (int64_t i = t; i < n; i += 1024) {
-    const double x = v[i];
-    if (finite_d(x)) {
-      cnt += 1.0;
-      sum += x;
-      mn = fmin(mn, x);
-      mx = fmax(mx, x);
-    }
-  }
-  sh[0][t] = cnt; sh[1][t] = sum; sh[2][t] = mn; sh[3][t] = mx;
-  __syncthreads();
-  for (int w = 512; w > 0; w >>= 1) {
-    if (t < w) {
-      sh[0][t] += sh[0][t + w];
-      sh[1][t] += sh[1][t + w];
-      sh[2][t] = fmin(sh[2][t], sh[2][t + w]);
-      sh[3][t] = fmax(sh[3][t], sh[3][t + w]);
-    }
-    __syncthreads();
-  }
-  const double N = sh[0][0], mean = N > 0 ? sh[1][0] / N : 0.0, vmin = sh[2][0], vmax = sh[3][0];
-  __syncthreads();
-  double s1 = 0, s2 = 0;
-  for (int64_t i = t; i < n; i += 1024) {
-    const double x = v[i];
-    if (finite_d(x)) {
-      const double d = x - mean;
-      s1 += d;
-      s2 += d * d;
-    }
-  }
-  sh[0][t] = s1; sh[1][t] = s2;
-  __syncthreads();
-  for (int w = 512; w > 0; w >>= 1) {
-    if (t < w) {
-      sh[0][t] += sh[0][t + w];
-      sh[1][t] += sh[1][t + w];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    double* o = ks + j * KS_LD;
-    o[0] = N; o[1] = mean; o[2] = sh[1][0]; o[3] = sh[0][0]; o[4] = vmin; o[5] = vmax; o[6] = 0; o[7] = 0;
-  }
-}
-
+// ------------------------------------------------------------------ key columns (k_key_stats: expr.h)
 // cell-major table: one gather brings all Q centred values of a cell.  flag |= 1 when the keys' masks differ in a cell.
 __global__ __launch_bounds__(256) void k_key_table(const double* __restrict__ V, int64_t n, int q, int Q,
                                                    const double* __restrict__ ks, double* __restrict__ tab,

@@ -6,7 +6,7 @@
 //
 //   sort (expr.h)      checks every code against [-1, n_bins); the cells sorted by level (CellListOf, expr.h), ascending inside a level
 //   k_cb_key_stats     per (key, level): finite count, mean, sum (v - mean), sum (v - mean)^2, min, max over the level's
-//                      cell list (fixed-order sums: k_key_stats of expr_corr.hip, segmented)
+//                      cell list (fixed-order sums: k_key_stats of expr.h, segmented)
 //   k_cb_key_table     cells x Q table of key values centred on the mean of the cell's own (key, level), 0 where the cell is
 //                      left out, + one word per cell: the keys that keep it (low 16 bits) and its level
 //   k_cb_dense         lane = gene, a workgroup walks a chunk (PB_DENSE_CHUNK cells) of one level's cell list; the cell, its
@@ -40,7 +40,7 @@ constexpr int CB_MAX_LEVELS = 1024;
 constexpr int CB_MAX_ROWS = 4096;     // q x levels, the row cap of cna_expr_to_bins
 using CellList = CellListOf<CB_MAX_LEVELS>;   // the sort's policy (expr.h)
 constexpr int CB_LDS_BYTES = 65536;   // what a kernel gets without opting in
-constexpr int KS_LD = 8;   // doubles per (key, level) in the key statistics: n, mean, sum vc^2, sum vc, min, max
+// KS_LD (expr.h) doubles per (key, level) in the key statistics: n, mean, sum vc^2, sum vc, min, max
 constexpr int WA_LD = 5;   // within-level sums per (key, gene): cov, var x, var v, a level with the gene / the key not constant
 
 // the sort with its codes and the chunks of the levels; the cell list; raw key columns, their table, the cells' words, the

@@ -1298,6 +1298,31 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_gene_corr(self.h, ptr(V), V.shape[0], ptr(out)), 'cna_gene_corr')
         return out
 
+    def nbhd_expr(self, genes, nsteps):
+        """Numerators (cells x len(genes)) and denominator (cells) of the neighbourhood-mean expression of the chosen
+        genes of the resident matrix after `nsteps` walk steps on the resident graph, float64, caller's cell order
+        (cna_nbhd_expr).  Needs `ensure_graph`, `colsums` and `ensure_expression`; the walk's state and the NAM stay."""
+        genes = np.ascontiguousarray(genes, dtype=np.int32)
+        n = self.expression_shape()['n_cells']
+        num = np.empty((n, genes.size))
+        den = np.empty(n)
+        check(self.lib.cna_nbhd_expr(self.h, ptr(genes), genes.size, int(nsteps), ptr(num), ptr(den)), 'cna_nbhd_expr')
+        return num, den
+
+    def gene_nbhd_corr(self, V, nsteps, timed=False):
+        """Pearson correlation of the neighbourhood-mean expression of every gene with every row of V (q x cells float64,
+        caller's cell order, NaN = cell left out), the mean and the population sd of the neighbourhood means, q x genes
+        float64 each, and the cells per key, int64 (cna_gene_nbhd_corr).  timed=True: also (fill, step, moments) in
+        milliseconds, the stream drained between the phases."""
+        V = _f64(V)
+        q, G = V.shape[0], self.expression_shape()['n_genes']
+        r, mean, sd = (np.empty((q, G)) for _ in range(3))
+        n_cells = np.zeros(q, dtype=np.int64)
+        times = np.zeros(3) if timed else None
+        check(self.lib.cna_gene_nbhd_corr(self.h, ptr(V), q, int(nsteps), ptr(r), ptr(mean), ptr(sd), ptr(n_cells), ptr(times)),
+              'cna_gene_nbhd_corr')
+        return (r, mean, sd, n_cells, times) if timed else (r, mean, sd, n_cells)
+
     def expr_to_bins(self, codes, n_bins, what):
         """Per-bin sums of the resident expression matrix (cna_expr_to_bins): `codes` int32 per cell in the caller's
         order, -1 = cell left out; `what` 0 sums x, 1 counts x > 0.  Returns (sums float64[n_bins, genes],

@@ -13,6 +13,7 @@ from ._gene_rank_corr import gene_rank_corr, gene_rank_corr_strata
 from ._gene_rank_perm import gene_rank_test
 from ._gene_rank_perm_strata import gene_rank_test_strata
 from ._nam_strata import nam_strata
+from ._gene_nbhd import gene_nbhd_corr, nbhd_expr
 from ._gene_sets import gene_set_enrich, gene_set_test
 
 __all__ = [
@@ -25,6 +26,7 @@ __all__ = [
     'gene_markers',
     'gene_markers_pairs',
     'gene_markers_within',
+    'gene_nbhd_corr',
     'gene_rank_corr',
     'gene_rank_corr_strata',
     'gene_rank_test',
@@ -35,6 +37,7 @@ __all__ = [
     'gene_test_strata',
     'nam',
     'nam_strata',
+    'nbhd_expr',
     'svd_nam',
     'diffuse',
     'diffuse_stepwise',

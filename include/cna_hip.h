@@ -638,7 +638,8 @@ int  cna_expr_upload_sparse(cna_ctx* ctx, const void* indptr, const void* indice
 /* Forget the resident d.X of that line (demo/demo.ipynb, "per-gene correlations to neighborhood coefficient") and the
  * work buffers of cna_gene_corr, cna_expr_to_bins, cna_expr_cross, cna_coef_strata, cna_gene_corr_by, cna_matrix_to_bins,
  * cna_enrichment_extremes, cna_expr_cross_by, cna_gram_by, cna_coef_raster, cna_graph_components_find,
- * cna_gene_ranksum_by, cna_gene_ranksum_pairs, cna_gene_ranksum_within, cna_gene_rank_corr and cna_gene_rank_corr_by: cna_ctx_device_bytes returns to what it was before the upload. */
+ * cna_gene_ranksum_by, cna_gene_ranksum_pairs, cna_gene_ranksum_within, cna_gene_rank_corr, cna_gene_rank_corr_by,
+ * cna_nbhd_expr and cna_gene_nbhd_corr: cna_ctx_device_bytes returns to what it was before the upload. */
 int  cna_expr_drop(cna_ctx* ctx);
 /* What is resident: *format 0 nothing, 1 the dense array, 2 gene-major lists; *n_uploads counts the uploads this context
  * has performed so far (it survives cna_expr_drop: callers check residency with it).  Any pointer may be NULL. */
@@ -1151,6 +1152,45 @@ int  cna_graph_components_find(cna_ctx* ctx, const int32_t* codes, int64_t n_cel
                                int64_t* n_kept_out, int64_t* totals_out, int* sweeps_out);
 int  cna_graph_components_list(cna_ctx* ctx, int64_t n_kept, int32_t* class_out, int32_t* size_out, int32_t* first_out);
 int  cna_graph_components_label(cna_ctx* ctx, const int32_t* rank, int64_t n_kept, int32_t* comp_out, int64_t n_cells);
+
+/* ---- neighbourhood-mean expression (csrc/expr_nbhd.hip) ---------------------------------------- */
+/* The gene side in the unit of the association's result.  cna.tl.association's coefficient is a number per
+ * NEIGHBOURHOOD: neighbourhood i is the soft set of cells that the nsteps-step random walk anchored at cell i reaches
+ * (_nam.py:21-41), and the NAM is the abundance of every sample in those sets (_nam.py:44-76).  With one step of that walk
+ *     c = A.sum(axis=0) + w                 (_nam.py:28)
+ *     P s = A.(s/c) + w*s/c                  (_nam.py:33)
+ * and e_g the column of gene g of the resident expression matrix widened to float64,
+ *     m_g = (P^nsteps e_g) / (P^nsteps 1)    element-wise
+ * is the mean of the gene over neighbourhood i with the weights the NAM uses: the numerator is what the NAM would hold if
+ * the gene were a sample, the denominator the neighbourhood's total membership mass.  A cell whose denominator is not a
+ * positive finite number is left out of every sum and its m is NaN.  w is the self weight of the last cna_colsums.
+ * The numerators and the denominator are, bit for bit, what cna_dense_load / nsteps x cna_dense_step / cna_dense_fetch
+ * return for the same columns on the same context (float32 and float64 graphs, any device cell order): the quotient s/c
+ * first, a row's stored entries in stored order, a multiply and then an add, no contraction.
+ *
+ * Both read the graph, the device's cell order and the column sums where they are and write only buffers of their own
+ * (freed by cna_expr_drop): the walk's state, the NAM, X and everything derived from them stay valid -- the NAM an
+ * association cached survives a call, and a call between the launch and the fetch of a local-null pass is fine.  They run on
+ * the expression stream behind whatever the main stream has queued and return once it has drained.
+ * CNA_ESTATE: no graph, no cna_colsums, no resident expression matrix, or a context with a communicator / a row block.
+ * CNA_EINVAL: the graph and the matrix differ in their cells; nsteps outside [1, 15]; q outside [1, 16]; m outside
+ * [1, 64] or a gene outside [0, n_genes).  CNA_ENOMEM: the tile buffers (2 x n_cells x 64 float64 and the per-cell
+ * columns) do not fit; nothing of the call is resident afterwards.
+ *
+ * cna_nbhd_expr: genes int32[m]; num_out n_cells x m row-major and den_out n_cells, float64, CALLER's cell order. */
+int  cna_nbhd_expr(cna_ctx* ctx, const int32_t* genes, int m, int nsteps, double* num_out, double* den_out);
+/* cna_gene_nbhd_corr: V as for cna_gene_corr (q x n_cells row-major, caller's cell order, NaN = cell left out).  Per gene
+ * and key over the cells where the key is finite and the denominator good (each key its own set; n_cells_out[j] of them):
+ *   r_out[j * n_genes + g]     Pearson correlation of m_g with column j, clipped to [-1, 1]
+ *   mean_out, sd_out           mean and population sd of m_g over those cells (same layout)
+ * in two passes over the tile while it is resident -- sum m; then sum (m - mean)^2 and sum (m - mean)(v - mean v) -- with
+ * partial sums per slab of rows added in slab order (no floating-point atomics: the same bits on every run).  r is NaN
+ * where numpy's 0 / 0 gives NaN (a constant key, fewer than two cells) and for a gene that is constant over ALL cells of the
+ * raw matrix, decided exactly: minimum == maximum with the implicit zeros counted.  times_ms_out: NULL, or 3 doubles
+ * that receive the milliseconds spent filling tiles, walking and on the moments (the stream is then drained between
+ * the phases: for measurements). */
+int  cna_gene_nbhd_corr(cna_ctx* ctx, const double* V, int q, int nsteps, double* r_out, double* mean_out, double* sd_out,
+                        int64_t* n_cells_out, double* times_ms_out);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* HIP-event timing of every kernel launch on the context's stream (bench.py roofline).  on = 1: every kernel group;
