@@ -129,6 +129,7 @@ SIGNATURES = {
     'cna_percell_fdr': (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'cna_matrix_shape': (C.c_int, [c_ctx, C.c_int, c_i64p, C.POINTER(C.c_int)]),
     'cna_fetch_matrix': (C.c_int, [c_ctx, C.c_int, C.c_void_p, C.c_int]),
+    'cna_fetch_nam_padding': (C.c_int, [c_ctx, C.c_void_p, C.POINTER(C.c_int)]),
     'cna_allgather_host': (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     'cna_prof_enable': (C.c_int, [c_ctx, C.c_int]),
     'cna_prof_reset': (C.c_int, [c_ctx]),

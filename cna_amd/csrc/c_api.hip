@@ -409,6 +409,22 @@ int cna_fetch_matrix(cna_ctx* c, int which, double* out, int transposed) {
   return 0;
 }
 
+// For tests: what stands in the padding columns N <= col < ld of the NAM's rows on the device (finish_row writes zeros
+// there; no other fetch reaches them).  The NAM only, not the state buffers.
+int cna_fetch_nam_padding(cna_ctx* c, double* out, int* n_pad_cols) {
+  CHECK_CTX(c);
+  AUTO_FINISH(c);
+  if (!n_pad_cols) CNA_FAIL(CNA_EINVAL, "cna_fetch_nam_padding: null pointer");
+  CNA_TRY(need_nam(c));
+  const int pad = c->ld - c->N;
+  *n_pad_cols = pad;
+  if (!out || pad <= 0 || c->n_local == 0) return 0;
+  HIP_TRY(hipMemcpy2DAsync(out, 8 * (size_t)pad, c->nam + c->N, 8 * (size_t)c->ld, 8 * (size_t)pad, c->n_local,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // cna_fetch_matrix with the rows (and columns) picked and ordered on the device: out[i][j] =
 // matrix[rows[i]][cols[j]], or its transpose.  which = CNA_MAT_NAM / CNA_MAT_X, or CNA_MAT_PROJ for the
 // result of the last cna_project_keep.  One gather kernel and one contiguous copy instead of a

@@ -1112,6 +1112,16 @@ class Engine(_order.CellOrder):
         check(self.lib.cna_fetch_matrix(self.h, which, ptr(out), int(bool(transposed))), 'cna_fetch_matrix')
         return out
 
+    def nam_padding(self):
+        """For tests: the padding columns N <= col < ld of the NAM's rows as they stand on the device (local rows x
+        (ld - N), device cell order); every walk step writes zeros there.  The NAM only, not the walk's state buffers."""
+        pad = C.c_int(0)
+        check(self.lib.cna_fetch_nam_padding(self.h, None, C.byref(pad)), 'cna_fetch_nam_padding')
+        out = np.empty((self.n_local, pad.value))
+        if out.size:
+            check(self.lib.cna_fetch_nam_padding(self.h, ptr(out), C.byref(pad)), 'cna_fetch_nam_padding')
+        return out
+
     def fetch_rows(self, which, rows=None, cols=None, transposed=False):
         """out[i, j] = M[rows[i], cols[j]] (None = all, in order) picked and ordered on the device;
         transposed=True returns the (columns x rows) layout.  which: MAT_NAM, MAT_X or MAT_PROJ."""

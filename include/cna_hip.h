@@ -518,6 +518,12 @@ void cna_host_draw_times(double* out2);
 int  cna_matrix_shape(cna_ctx* ctx, int which, int64_t* n_rows_local, int* n_cols);
 /* transposed!=0 writes samples x cells (the reference's orientation), else cells x samples */
 int  cna_fetch_matrix(cna_ctx* ctx, int which, double* out, int transposed);
+/* FOR TESTS.  The analysis never calls this.  The NAM's rows are ld = round_up(N, 4) doubles apart on the device; every
+ * walk step writes zeros into the padding columns N <= col < ld of the rows it stores, and no other fetch reaches them.
+ * *n_pad_cols = ld - N; out (n_local x n_pad_cols, may be NULL to ask for the count alone) receives those columns of
+ * every local row of the NAM, in device cell order.  The NAM only: the padding of the walk's state buffers, which the
+ * step kernels write the same way, is not read back.  CNA_ESTATE without a NAM. */
+int  cna_fetch_nam_padding(cna_ctx* ctx, double* out, int* n_pad_cols);
 /* the same with rows and columns picked and ordered on the device: out[i][j] = M[rows[i]][cols[j]]
  * (n_out x n_cols, or its transpose); rows / cols NULL = all, in order.  rows are local row indices
  * of the matrix.  One gather kernel + one contiguous copy: the caller's cell order and orientation

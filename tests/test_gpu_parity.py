@@ -1021,7 +1021,9 @@ def test_fused_selection_call_equals_separate_calls(eng, monkeypatch):
 
 @pytest.mark.parametrize('n,N,nsteps,ncov', [(20011, 200, 3, 0), (5000, 100, 3, 0), (9999, 233, 2, 0), (3001, 66, 4, 0),
                                              (2500, 300, 3, 0), (40, 180, 3, 0), (4000, 64, 3, 0), (7001, 200, 3, 5),
-                                             (3000, 90, 5, 2)])
+                                             (3000, 90, 5, 2),
+                                             # wide states: NQ2 = 4, 6 (U = 4) and 8 of k_nam_step with the by-product
+                                             (1400, 385, 3, 0), (1400, 513, 3, 0), (1600, 769, 3, 0), (1800, 1024, 4, 0)])
 def test_selection_as_a_by_product_of_the_last_walk_step(eng, monkeypatch, n, N, nsteps, ncov):
     """More than 64 samples, every cell and sample kept, nothing regressed out: the last step of the walk also does the
     selection pass (_association.py:182 zero-variance count, _nam.py:122,159 centre and / std, _association.py:77
